@@ -22,6 +22,11 @@ timed jobs, stamped from inside the kernel (dsx_stamps_begin/end:
 s_memrealtime at the first wave's first and the last wave's last
 instruction), with nothing added between the launches.
 
+A plain run sets up, warms up, times --steps steps and prints the line.
+--dump-outputs DIR also writes the last timed step's cut list as .npy (the
+blob is seeded, so two builds can be compared cut for cut); --full adds the
+cpu_baseline leg, which the headline figure does not need.
+
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
 from __future__ import annotations
@@ -43,6 +48,7 @@ MIN, AVG, MAX = 16 * 1024, 64 * 1024, 256 * 1024
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table: 8.0 TB/s spec
 PIECE = 8 * GiB          # bytes per scan launch (the engine's piece, kPieceMax)
 CPU_SAMPLE = GiB         # cpu_baseline: the first GiB of the shard
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all ranks' files together stay under 64 MB
 METRIC = "GiB/s chunked (device-resident blob→cut list), 16/64/256KiB, 1/2/4/8 MI355X"
 
 
@@ -66,7 +72,15 @@ def parse():
                     help="average chunk size in KiB, min = avg/4, max = 4*avg (SURVEY.md 8(d)'s "
                          "sweep 16/64/256, chunker_test.go:191's set); default 64 = desync make's "
                          "16/64/256 KiB")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not "
+                         "need: the cpu_baseline leg (N = 1; 10-30 s of host work)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR as .npy files: this "
+                         "rank's cut list (chunk end offsets, float64: exact below 2^53) as "
+                         "cuts.npy, cuts_rank<r>.npy at N > 1")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the cpu_baseline leg (0: the job's CPU share)")
     ap.add_argument("--inflight", type=int, default=0,
@@ -80,6 +94,8 @@ def parse():
                     help="write {t0, t1, bytes} (unix time around the timed steps) to this "
                          "file, for tools/smu_summary.py's energy window")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config2:
         args.workload, args.gib, args.seed = "uniform", args.gib or 1.0, args.seed or 1
     elif args.config5:
@@ -259,6 +275,18 @@ def hbm_footprint(torch, blob, outs, ctxs):
             "device_free_bytes": free, "frac_of_device": round(used / total, 4)}
 
 
+def dump_cuts(d, name, cuts, max_bytes):
+    """--dump-outputs: one cut list as d/<name>.npy in float64.  A list over
+    max_bytes is cut down to a fixed sample (seed 0, positions in order), the
+    same for every run of the same arguments."""
+    a = np.asarray(cuts).astype(np.float64)
+    keep = max_bytes // a.itemsize
+    if a.size > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), a)
+
+
 def dist_info(dist, backend, per_rank):
     """What torch.distributed reports for the job: the backend of the
     default group, its world size and, over RCCL, the library version."""
@@ -427,6 +455,14 @@ def main():
         with open(args.marks, "w") as f:
             json.dump({"t0": wall0, "t1": wall1, "bytes": n * args.steps, "rank": rank}, f)
     stamps = [st for c in stamp_ctxs for st in c.stamps_end()] if stamping else []
+    if args.dump_outputs:
+        # the last timed step's cut list, as its caller reads it from HBM
+        if world == 1:
+            last = outs[(args.steps - 1) % depth][:chunks].cpu().numpy()
+        else:
+            last = lanes[(args.steps - 1) % len(lanes)].cuts()
+        dump_cuts(args.dump_outputs, "cuts" if world == 1 else f"cuts_rank{rank}", last,
+                  DUMP_MAX_BYTES // world)
     mine = {"rank": rank, "roofline": roofline_of(stamps, dt, args.workload), "hbm": hbm_footprint(
         torch, blob, outs + ([sh.out for sh in lanes] if lanes else []), stamp_ctxs)}
     per_rank = [mine]
@@ -500,7 +536,7 @@ def main():
         if dist:
             res["dist"] = dist_info(dist, backend, per_rank)
             res["dist"]["ranks_counted_by_backend"] = ranks_counted
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             # a bounded sample: the shard's first GiB (the leg is ~10-30 s of CPU work)
             host = blob[halo:halo + min(n, CPU_SAMPLE)].cpu().numpy()
             res["cpu_baseline"] = cpu_baseline(host, args.cpu_threads or None)

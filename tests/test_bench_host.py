@@ -58,6 +58,33 @@ def test_traffic_lookup_by_launch_size(tmp_path, monkeypatch):
     assert bench.load_traffic("uniform", 128) is None
 
 
+def test_plain_run_leaves_the_cpu_leg_to_full(monkeypatch):
+    """A plain run does what the headline figure needs; the cpu_baseline leg
+    is behind --full, and --dump-outputs is off unless asked for."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.no_cpu) == (True, "d", False)
+
+
+def test_dump_cuts_writes_float64_within_its_budget(tmp_path):
+    """--dump-outputs: the cut list itself in float64 (offsets are exact), or
+    the same seeded sample of it on every run when it is over the budget."""
+    cuts = np.cumsum(np.arange(1, 1001, dtype=np.uint64) << np.uint64(25))
+    d = str(tmp_path / "out")
+    bench.dump_cuts(d, "cuts", cuts, 1 << 20)
+    a = np.load(tmp_path / "out" / "cuts.npy")
+    assert a.dtype == np.float64 and np.array_equal(a.astype(np.uint64), cuts)
+    bench.dump_cuts(d, "some", cuts, 800)
+    s = np.load(tmp_path / "out" / "some.npy")
+    assert s.dtype == np.float64 and s.size == 100 and np.all(np.diff(s) > 0)
+    assert np.isin(s.astype(np.uint64), cuts).all()
+    bench.dump_cuts(d, "again", cuts, 800)
+    assert np.array_equal(np.load(tmp_path / "out" / "again.npy"), s)
+
+
 def test_cpu_leg_matches_the_sequential_chain():
     """What the baseline times is the reference's result: split-and-align ==
     the sequential Next loop (make_test.go:16-80)."""

@@ -136,6 +136,29 @@ def test_bench_two_ranks_gloo_check():
     assert r0["blob_bytes"] == int(0.25 * (1 << 30))
 
 
+def test_bench_plain_run_dumps_its_last_cut_list(tmp_path):
+    """bench.py --gpus 1 --dump-outputs: cuts.npy is the cut list of the last
+    timed job (float64, every offset exact), equal to the oracle's sequential
+    chunking of the same seeded blob; a plain run times exactly --steps jobs
+    and leaves the cpu_baseline leg to --full."""
+    from oracle import oracle as o
+    n = 64 << 20
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5",
+           "--warmup", "1", "--gib", str(n / (1 << 30)), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 5 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+    assert line["roofline"]["launches"] == 5  # one scan launch per timed job at this size
+    assert abs(line["value"] - n / (1 << 30) / (line["ms_per_step"] / 1e3)) <= 0.01 * line["value"]
+    assert os.listdir(tmp_path / "out") == ["cuts.npy"]
+    cuts = np.load(tmp_path / "out" / "cuts.npy")
+    ref = o.chunk_stream(o.synth_uniform_c(3, 0, n), MIN, AVG, MAX)
+    assert cuts.dtype == np.float64 and line["config"]["chunks"] == ref.size
+    assert np.array_equal(cuts.astype(np.uint64), ref)
+
+
 def test_context_device_bytes_accounts_for_its_hbm():
     """dsx_stats_t.device_bytes (bench.py's per-rank HBM footprint) covers
     what the device lost to the context: hipMemGetInfo's drop across

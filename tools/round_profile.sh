@@ -18,7 +18,7 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 || { tail -40 $OUT/pytest_gpu.log; exit 1; }
   tail -2 $OUT/pytest_gpu.log
 fi
-timeout -k 10 300 python3 tools/smu_sample.py $OUT/smu_bench.jsonl -- python3 $CMD --marks $OUT/bench.marks.json > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 300 python3 tools/smu_sample.py $OUT/smu_bench.jsonl -- python3 $CMD --full --marks $OUT/bench.marks.json > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 python3 tools/smu_summary.py $OUT/smu_bench.jsonl $OUT/bench.marks.json > $OUT/smu_bench.json && cat $OUT/smu_bench.json
 timeout -k 10 200 python3 $CMD --no-cpu > $OUT/bench_2.json 2> $OUT/bench_2.err || { tail $OUT/bench_2.err; exit 1; }
