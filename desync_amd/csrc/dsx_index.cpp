@@ -744,6 +744,102 @@ struct IndexGeom {
 // last stitch against 2.04 / 1.89 / 2.07).
 uint64_t share_end_cut(uint64_t fcut) { return std::max<uint64_t>(kFeedCutBase, (fcut * 11 / 16) & ~4095ull); }
 
+// run_index's schedule, decided before the read starts and executed by its
+// read loop as it stands here: where a scan + stitch follows the pieces, which
+// planned shares fire and where, and who hashes what in the last window.  The
+// window's IDs come from three parties -- the GPU's shares, the feeder and the
+// digest after the read -- that divide each segment's chunks by length at one
+// cut: the GPU skips the chunks above it, the feeder takes exactly those.
+// Both sides read that cut from the same ShareSeg, so no chunk is left
+// between two cuts.
+//   scan    the piece ends a scan + stitch follows: a window's end, every
+//           scan_step bytes, every piece of the fine tail;
+//   mids    the planned shares (plan_shares; `at` absolute); fire[k] is the
+//           scan point share k fires at, 0: dropped.  A share fires at the
+//           first scan point at or after its `at` that is below len and after
+//           the previous share's (one per scan point: each has a snapshot and
+//           a side stream of its own).  One that could fire only at len would
+//           hash nothing during the read: it is dropped, and neither the
+//           feeder nor the last digest ever sees its cut.  (Until round 7 the
+//           feeder was built with the cuts of all planned shares and the last
+//           digest with fcut_end: with a slot large enough that no scan point
+//           below len followed a share's `at`, the last segment's chunks
+//           between the two cuts were hashed by nobody.)
+//   fired   the shares that fire, in order: {scan point, cut}; share j runs on
+//           side stream side0 + j (side stream 0 carries the previous
+//           window's digest when there is one);
+//   segs    the last window's bytes [last_ws, len) cut at the fired shares'
+//           scan points; a chunk belongs to the segment its end lies in
+//           (from, to].  Segment j < fired.size() is share j's; the last one
+//           is the digest's after the read, which starts from the last fired
+//           share's snapshot (the window's start without one).  feed_cut
+//           UINT64_MAX: no feeder; skip_above 0: the GPU hashes every chunk
+//           (a share's cut of max or more).
+struct ShareSeg {
+  uint64_t from, to, feed_cut, skip_above;
+};
+struct IndexSchedule {
+  bool feed_on = false;  // the last window has a tail feeder
+  uint64_t last_ws = 0, fcut = 0, fcut_end = 0;
+  size_t side0 = 0;
+  std::vector<uint64_t> scan;
+  std::vector<Mid> mids, fired;
+  std::vector<uint64_t> fire;
+  std::vector<ShareSeg> segs;
+};
+IndexSchedule index_schedule(const IndexGeom& g, uint64_t len, uint64_t max_chunk, int threads,
+                             int64_t host_tail, bool feeds) {
+  IndexSchedule s;
+  const PieceMap pm(len, g.piece, g.fine_from, g.fine);
+  const uint64_t scan_step = std::max<uint64_t>(g.piece, kScanStep / g.piece * g.piece);
+  for (uint64_t k = 0, scanned = 0; k < pm.np; ++k) {
+    const uint64_t end = pm.off(k) + pm.size(k);
+    const uint64_t wend = std::min(len, (end - 1) / g.W * g.W + g.W);  // its window's end
+    if (end == wend || end - scanned >= scan_step || end > g.fine_from) {
+      s.scan.push_back(end);
+      scanned = end;
+    }
+  }
+  s.last_ws = (g.nwin - 1) * g.W;
+  s.side0 = g.nwin > 1 ? 1 : 0;
+  s.fcut = s.fcut_end = feed_cut_for(host_tail, threads);
+  s.feed_on = feeds;
+  // (several windows: the last one's shares, on side streams 1..)
+  bool share_multi = true;
+#if DSX_DIAG
+  if (g.nwin > 1 && getenv("DSX_FEED_MULTI") && atoi(getenv("DSX_FEED_MULTI")) == 0) s.feed_on = false;
+  if (const char* v = getenv("DSX_SHARE_MULTI")) share_multi = atoi(v) != 0;
+#endif
+  if (s.feed_on && (g.nwin == 1 || share_multi) && host_tail < 0) {
+    s.mids = plan_shares(len - s.last_ws, max_chunk, s.fcut);
+    if (s.mids.size() > (size_t)dsx_ctx::kIdxSide - s.side0) s.mids.resize(dsx_ctx::kIdxSide - s.side0);
+    for (Mid& m : s.mids) m.at += s.last_ws;
+    s.fire.assign(s.mids.size(), 0);
+    for (uint64_t sp : s.scan) {
+      if (sp <= s.last_ws) continue;
+      const size_t m = s.fired.size();
+      if (sp >= len || m == s.mids.size()) break;
+      if (sp >= s.mids[m].at) {
+        s.fire[m] = sp;
+        s.fired.push_back({sp, s.mids[m].cut});
+      }
+    }
+    if (!s.fired.empty()) {
+      s.fcut_end = share_end_cut(s.fcut);
+#if DSX_DIAG
+      if (const char* v = getenv("DSX_FEED_CUT_END")) s.fcut_end = std::max<uint64_t>(4096, atol(v));
+#endif
+    }
+  }
+  uint64_t from = s.last_ws;
+  for (const Mid& m : s.fired) {
+    s.segs.push_back({from, m.at, m.cut, m.cut >= max_chunk ? 0 : m.cut});
+    from = m.at;
+  }
+  s.segs.push_back({from, len, s.feed_on ? s.fcut_end : UINT64_MAX, s.feed_on ? s.fcut_end : 0});
+  return s;
+}
+
 int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn fill, void* ud,
               uint64_t* out_ends, uint8_t* out_ids, uint64_t cap, uint64_t* n_out,
               const uint8_t* direct = nullptr) {
@@ -760,7 +856,10 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
   const IndexGeom g(len, p->max, c->index_slot, c->index_window, feeds);
   const uint64_t pre = g.pre, piece = g.piece, W = g.W, nwin = g.nwin;
   const uint64_t fine = g.fine, fine_from = g.fine_from;
-  const uint64_t scan_step = std::max<uint64_t>(piece, kScanStep / piece * piece);
+  const int fth = feed_threads(c);
+  // the scan points, the shares that fire and every segment's cut, for the
+  // read loop, the feeder and the last digest alike
+  const IndexSchedule sc = index_schedule(g, len, p->max, fth, c->index_host_tail, feeds);
   rc = index_setup(c, piece);
   if (rc) return rc;
   HIPCHK(c, grow(c, c->idx_win[0], pre + W));
@@ -830,8 +929,6 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
     } feed_ev;
     if (tail_on) HIPCHK(c, hipEventCreateWithFlags(&feed_ev.e, hipEventDisableTiming));
     std::unique_ptr<TailFeeder> feed;
-    const int fth = feed_threads(c);
-    const uint64_t fcut = feed_cut(c, fth);
     // the readers' CPUs join the feeder's hashers once the reads are done
     int feed_extra = std::max(0, std::min(c->index_readers, host_cpu_share() - fth));
 #if DSX_DIAG
@@ -860,45 +957,27 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
     // (A first form gave the GPU every chunk of the first half and started
     // the feeder at mid: the host then had less time for the same work, 0.66-
     // 0.72 x dsx_cut_fd against 0.78, profiles/r06e, r06f.)
-    uint64_t fcut_end = fcut;
+    // (Which shares fire, at which scan point, and each segment's cut on
+    // both sides: index_schedule, computed above; this loop executes it.)
     int share_pc = 1;
 #if DSX_DIAG
     if (const char* v = getenv("DSX_SHARE_PC")) share_pc = atoi(v);
 #endif
     // (several windows: the last one's shares, on side streams 1.. -- side
     // stream 0 carries the previous window's digest meanwhile)
-    bool share_multi = true;
-#if DSX_DIAG
-    if (const char* v = getenv("DSX_SHARE_MULTI")) share_multi = atoi(v) != 0;
-#endif
-    const uint64_t last_ws = (nwin - 1) * W, last_wl = len - last_ws;
-    const size_t side0 = nwin > 1 ? 1 : 0;  // the first side stream of the shares
-    std::vector<Mid> mids;
-    if (tail_on && (nwin == 1 || share_multi) && c->index_host_tail < 0) {
-      fcut_end = share_end_cut(fcut);
-#if DSX_DIAG
-      if (const char* v = getenv("DSX_FEED_CUT_END")) fcut_end = std::max<uint64_t>(4096, atol(v));
-#endif
-      mids = plan_shares(last_wl, p->max, fcut);
-      if (mids.size() > (size_t)dsx_ctx::kIdxSide - side0) mids.resize(dsx_ctx::kIdxSide - side0);
-      for (Mid& m : mids) m.at += last_ws;
-      if (mids.empty()) fcut_end = fcut;
-    }
-    std::vector<Ev> mid_ev(mids.size());
+    const size_t side0 = sc.side0;  // the first side stream of the shares
+    std::vector<Ev> mid_ev(sc.fired.size());
     for (auto& x : mid_ev) HIPCHK(c, hipEventCreateWithFlags(&x.e, hipEventDisableTiming));
-    size_t mids_done = 0;
-    // snapshot k: after the piece at mids[k].at (the window's start is idx_snap[0])
+    size_t mids_done = 0, scans_done = 0;
+    // snapshot k: after the piece share k fires at (the window's start is idx_snap[0])
     auto mid_snap = [&](size_t k) { return c->idx_snap.p + 2 * (nwin + 1 + k); };
     for (w = 0; w < nwin; ++w) {
       ws = w * W;
       wl = std::min(W, len - ws);
       uint8_t* buf = c->idx_win[w & 1].p;
-      bool feed_on = tail_on && w + 1 == nwin;
-#if DSX_DIAG
-      if (nwin > 1 && getenv("DSX_FEED_MULTI") && atoi(getenv("DSX_FEED_MULTI")) == 0) feed_on = false;
-#endif
+      const bool feed_on = sc.feed_on && w + 1 == nwin;
       if (feed_on) {
-        feed.reset(new TailFeeder(c, tsrc, len, mids.empty() ? fcut : mids[0].cut, fth,
+        feed.reset(new TailFeeder(c, tsrc, len, sc.segs[0].feed_cut, fth,
                                   (pre + wl) / p->min + 2, c->piece_seq, nwin > 1 ? feed_ev.e : nullptr,
                                   c->idx_snap.p + 2 * w, feed_extra));
       }
@@ -924,7 +1003,8 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
         if (e != hipSuccess) return drain(c, pf, set_hip_err(c, e, "index: H2D"));
         if (k >= 1) pf.release(k - 1);
         const uint64_t end = off + hn;
-        if (end == ws + wl || end - scanned >= scan_step || end > fine_from) {
+        if (scans_done < sc.scan.size() && end == sc.scan[scans_done]) {
+          ++scans_done;
           e = scan_wait(c, c->idx_copy_ev[k % K]);  // (the stitch follows the scan)
           if (e != hipSuccess) return drain(c, pf, set_hip_err(c, e, "index: wait"));
           const uint64_t halo = w == 0 ? scanned : pre + (scanned - ws);
@@ -934,11 +1014,12 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
           c->timing = true;
           if (rc) return drain(c, pf, rc);
           scanned = end;
-          if (mids_done < mids.size() && end >= mids[mids_done].at && end < len && feed) {
+          if (mids_done < sc.fired.size() && end == sc.fired[mids_done].at && feed) {
             // the GPU's share of segment k: chunks [snap[k-1].total,
             // snap[k].total) up to its cut, on the digest stream, on 3/4 of
             // the CUs (the rest keep room for the next pieces' scans)
             const size_t m = mids_done++;
+            const ShareSeg& seg = sc.segs[m];
             hipLaunchKernelGGL(state_snapshot_kernel, dim3(1), dim3(64), 0, c->stream,
                                (const DevState*)c->state.p, mid_snap(m));
             e = hipEventRecord(mid_ev[m].e, c->stream);
@@ -951,23 +1032,22 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
             dm.ids = c->dg_ids.p;
             dm.range_lo = m ? mid_snap(m - 1) : c->idx_snap.p + 2 * w;
             dm.range_hi = mid_snap(m);
-            dm.skip_above = mids[m].cut >= p->max ? 0 : mids[m].cut;
+            dm.skip_above = seg.skip_above;
             // (on its own side stream after this stitch: the shares run side by side)
             hipStream_t ss = c->idx_side[side0 + m];
             e = hipStreamWaitEvent(ss, mid_ev[m].e, 0);
             if (e != hipSuccess) return drain(c, pf, set_hip_err(c, e, "index: wait"));
             // (digest_pc_kernel: its chain ran ~45 ns/B during the read,
             // digest_kernel's ~85, profiles/r06aa, r06ab)
-            const uint64_t from = m ? mids[m - 1].at : ws;
-            rc = launch_digest(c, dm, (end - from + 2 * p->max) / p->min + 2, algo, ss,
+            rc = launch_digest(c, dm, (end - seg.from + 2 * p->max) / p->min + 2, algo, ss,
                                c->idx_side_q.p + 32 * (side0 + m), false, (uint32_t)(c->ncu * 3 / 4),
                                share_pc);
             if (rc) return drain(c, pf, rc);
-            feed->add_boundary(mid_ev[m].e, mid_snap(m), m + 1 < mids.size() ? mids[m + 1].cut : fcut_end);
+            feed->add_boundary(mid_ev[m].e, mid_snap(m), sc.segs[m + 1].feed_cut);
 #if DSX_DIAG
             if (getenv("DSX_TAIL_LOG"))
               fprintf(stderr, "index: GPU share %zu up to %.1f MB (cut %lu), %.2f ms into the call\n",
-                      m, end / 1e6, (unsigned long)mids[m].cut,
+                      m, end / 1e6, (unsigned long)seg.feed_cut,
                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call_t0).count());
 #endif
           }
@@ -977,6 +1057,11 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - call_t0).count());
 #endif
         }
+      }
+      // (the schedule's scan points end every window, and its shares have all fired)
+      if (scanned != ws + wl || (w + 1 == nwin && mids_done != sc.fired.size())) {
+        c->err = "index: the read loop left the schedule";
+        return drain(c, pf, DSX_E_INTERNAL);
       }
       // the window's finished chunks: [snap[w].total, snap[w+1].total) from
       // snap[w].carry, all inside this window's bytes
@@ -1018,7 +1103,10 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
           // window's chunks up to the cut, so that a window's ~10 K of them
           // run on digest_pc_kernel (its chain ~38 ns/B at the end of a call,
           // digest_kernel's ~58; profiles/r06aa)
-          da.skip_above = fcut_end;
+          // (the last segment's cut, the one the feeder has used since the
+          // last share that fired: index_schedule)
+          const uint64_t fcut_end = sc.segs.back().feed_cut;
+          da.skip_above = sc.segs.back().skip_above;
           uint64_t short_n = 0;
           for (uint64_t i = 0, st = snap[1]; i < ends.size(); st = ends[i++]) short_n += ends[i] - st <= fcut_end;
           // (its own queue counter: the previous window's digest may still
@@ -1433,6 +1521,45 @@ extern "C" uint64_t dsx_diag_index_pieces(uint64_t len, uint64_t max_chunk, uint
     size[k] = pm.size(k);
   }
   return pm.np;
+}
+// The schedule run_index executes (index_schedule) for a SHA-512/256 call
+// with IDs on an AVX-512 host (the tail feeder on unless host_tail is 0), at
+// `threads` feeder threads.  scan[0, *n_scan): the scan points (at most
+// scan_cap written).  at/cut/fire[k]: planned share k, absolute, and the scan
+// point it fires at (0: dropped); returns their count (at most share_cap
+// written).  seg[4 j ..]: {from, to, the feeder's cut, the GPU's skip_above}
+// of the last window's segment j < *n_seg (at most seg_cap written).
+// info: {the last window's start, the first side stream of the shares, the
+// feeder's usual cut, the last segment's cut, the side streams}.
+extern "C" int dsx_diag_index_schedule(uint64_t len, uint64_t max_chunk, uint64_t slot, uint64_t window,
+                                       int threads, int64_t host_tail, uint64_t* scan,
+                                       uint64_t scan_cap, uint64_t* n_scan, uint64_t* at, uint64_t* cut,
+                                       uint64_t* fire, int share_cap, uint64_t* seg, int seg_cap,
+                                       int* n_seg, uint64_t* info) {
+  if (len == 0) return -1;
+  const bool feeds = host_tail != 0;
+  const IndexGeom g(len, max_chunk, slot, window, feeds);
+  const IndexSchedule s = index_schedule(g, len, max_chunk, threads, host_tail, feeds);
+  *n_scan = s.scan.size();
+  for (uint64_t i = 0; i < s.scan.size() && i < scan_cap; ++i) scan[i] = s.scan[i];
+  for (size_t k = 0; k < s.mids.size() && (int)k < share_cap; ++k) {
+    at[k] = s.mids[k].at;
+    cut[k] = s.mids[k].cut;
+    fire[k] = s.fire[k];
+  }
+  *n_seg = (int)s.segs.size();
+  for (size_t j = 0; j < s.segs.size() && (int)j < seg_cap; ++j) {
+    seg[4 * j] = s.segs[j].from;
+    seg[4 * j + 1] = s.segs[j].to;
+    seg[4 * j + 2] = s.segs[j].feed_cut;
+    seg[4 * j + 3] = s.segs[j].skip_above;
+  }
+  info[0] = s.last_ws;
+  info[1] = s.side0;
+  info[2] = s.fcut;
+  info[3] = s.fcut_end;
+  info[4] = (uint64_t)dsx_ctx::kIdxSide;
+  return (int)s.mids.size();
 }
 #endif
 

@@ -158,27 +158,40 @@ def test_index_host_tail_gpu_shares(tmp_path, monkeypatch, mib, cut1):
     data = o.synth_uniform_c(48, 0, n)
     f = tmp_path / "blob"
     data.tofile(str(f))
-    ctx = _lib.Context(0)
-    try:
-        fd = os.open(str(f), os.O_RDONLY)
+    ref = o.chunk_parallel(data, MIN, AVG, MAX, o.default_threads())
+    # The four calls share one context and its ID buffer: an ID a call fails
+    # to write would still be the previous call's correct one.  Before each,
+    # the buffer is filled with the IDs of a primer (the same length, another
+    # seed): over the reference's list, then through the same entry point.
+    primer = o.synth_uniform_c(84, 0, n)
+    g = tmp_path / "primer"
+    primer.tofile(str(g))
+
+    def on_fd(path, fn):
+        fd = os.open(str(path), os.O_RDONLY)
         try:
-            ends, ids = desync_amd.index_fd(fd, MIN, AVG, MAX, ctx=ctx)
+            return fn(fd)
         finally:
             os.close(fd)
+
+    ctx = _lib.Context(0)
+    try:
+        desync_amd.ids_host(primer, 0, ref, ctx=ctx)
+        on_fd(g, lambda fd: desync_amd.index_fd(fd, MIN, AVG, MAX, ctx=ctx))
+        ends, ids = on_fd(f, lambda fd: desync_amd.index_fd(fd, MIN, AVG, MAX, ctx=ctx))
         n_host = ctx.stats().host_tail_chunks
+        desync_amd.ids_host(primer, 0, ref, ctx=ctx)
+        desync_amd.index_host(primer, MIN, AVG, MAX, ctx=ctx)
         ends2, ids2 = desync_amd.index_host(data, MIN, AVG, MAX, ctx=ctx)
         # VerifyIndex of the same list (run_ids' shares: the chunk ranges known
         # on the host, the last segment's chunks above a budgeted cut on the
         # host from the call's start)
-        fd = os.open(str(f), os.O_RDONLY)
-        try:
-            vids = desync_amd.ids_fd(fd, 0, ends, ctx=ctx)
-        finally:
-            os.close(fd)
+        on_fd(g, lambda fd: desync_amd.ids_fd(fd, 0, ref, ctx=ctx))
+        vids = on_fd(f, lambda fd: desync_amd.ids_fd(fd, 0, ends, ctx=ctx))
+        desync_amd.ids_host(primer, 0, ref, ctx=ctx)
         vids2 = desync_amd.ids_host(data, 0, ends, ctx=ctx)
     finally:
         ctx.close()
-    ref = o.chunk_parallel(data, MIN, AVG, MAX, o.default_threads())
     assert np.array_equal(ends, ref) and np.array_equal(ends2, ref)
     starts = np.concatenate([[0], ref[:-1]]).astype(np.uint64)
     mv = memoryview(data)

@@ -407,19 +407,19 @@ def test_smu_summary_window():
     assert abs(out["res_ppt"] - 350 / 750) < 0.01  # (PPT active over samples 200..599)
 
 
+def _index_sched():
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "index_sched.py")
+    spec = importlib.util.spec_from_file_location("index_sched", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def _diag_lib():
-    import ctypes
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "desync_amd",
-                        "libdsx_diag.so")
-    if not os.path.exists(path):
+    lib = _index_sched().diag_lib()
+    if lib is None:
         pytest.skip("libdsx_diag.so not built (make -C desync_amd/csrc diag)")
-    lib = ctypes.CDLL(path)
-    u64p = ctypes.POINTER(ctypes.c_uint64)
-    lib.dsx_diag_index_plan.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, u64p, u64p,
-                                        u64p, u64p, ctypes.c_int]
-    lib.dsx_diag_index_plan.restype = ctypes.c_int
-    lib.dsx_diag_index_pieces.argtypes = [ctypes.c_uint64] * 4 + [ctypes.c_int, u64p, u64p, ctypes.c_uint64]
-    lib.dsx_diag_index_pieces.restype = ctypes.c_uint64
     return lib
 
 
@@ -481,3 +481,143 @@ def test_index_piece_map():
                 # the small pieces are the file's last 32 MiB (rounded down to
                 # a slot), inside its last window
                 assert all(off[k] >= length - (32 << 20) - piece for k in fine), (length, feeds)
+
+
+# ------------------------------------------- run_index's schedule (no GPU)
+_MiB = 1 << 20
+_TRACED = (352 << 20) + 4321  # (two shares at 28 feeder threads: ~176 MiB, cut 90112; ~264 MiB, cut 45056)
+_SWEEP_SLOTS = (256 << 10, 1 << 20, 32 << 20, 288 << 20, 512 << 20, 900 << 20, None)  # None: the file's length
+_SWEEP_WINDOWS = (1 << 30, 80 << 20)
+
+
+def _sweep_lengths():
+    import random
+    rnd = random.Random(5)
+    cases = [1, 4095, 4096, 8 << 20, (32 << 20) + 1, 1 << 30, (1 << 30) + 12345, (3 << 30) - 7]
+    cases += [rnd.randrange(1, 5 << 30) for _ in range(40)]  # (test_index_piece_map's)
+    cases += [5 << 30, _TRACED, (80 << 20) + 4321, (160 << 20) + 4321, (640 << 20) + 4321,
+              (1 << 30) + (352 << 20) + 4321]
+    return cases
+
+
+@pytest.mark.parametrize("window", _SWEEP_WINDOWS)
+@pytest.mark.parametrize("slot", _SWEEP_SLOTS)
+def test_index_schedule_sweep(slot, window):
+    """The schedule run_index executes (dsx_index.cpp index_schedule, through
+    dsx_diag_index_schedule) over lengths from 1 B to 5 GiB x 1, 12 and 28
+    feeder threads, per read slot and HBM window (80 MiB windows put the
+    shares into the last of several): the segments tile the last window; in
+    every segment the feeder's cut is the GPU's skip_above (a cut of max or
+    more: the GPU takes the segment whole); every planned share fires at a
+    scan point below len at or after its point, or its cut never reaches the
+    feeder; the fired shares are in order, one side stream each, side stream
+    0 left to the previous window's digest; and the digest after the read
+    starts at the last fired share's snapshot.  The scan points are the piece
+    ends dsx_diag_index_pieces gives.  A schedule that breaks one of these
+    leaves chunk IDs hashed by nobody (or twice) with return code 0."""
+    S = _index_sched()
+    lib = _diag_lib()
+    bad, with_shares, dropped = [], 0, 0
+    for length in _sweep_lengths():
+        sl = max(4096, slot or length)
+        ends = {o + n for o, n in S.pieces(lib, length, sl, window)}
+        for threads in (1, 12, 28):
+            s = S.schedule(lib, length, sl, window, threads)
+            v = S.violations(s, length)
+            if not set(s["scan"]) <= ends:
+                v.append("a scan point is no piece end")
+            if v:
+                bad.append((length, threads, v))
+            with_shares += bool(s["shares"])
+            dropped += any(not f for _, _, f in s["shares"])
+    assert not bad, f"{len(bad)} schedules: " + "; ".join(f"len {n} threads {t}: {v[0]}" for n, t, v in bad[:12])
+    if window == 1 << 30 and (slot or 0) <= 32 << 20:  # (the sweep reaches the shares at all)
+        assert with_shares > 20, with_shares
+    if slot is None or (slot == 288 << 20 and window == 1 << 30):  # (and the shares that cannot fire)
+        assert dropped > 0
+
+
+@pytest.mark.parametrize("name,length,slot,threads,scan,fire,segs", [
+    # the issue's two traced geometries: 28 feeder threads, fcut = fcut_end =
+    # 28672, shares planned at ~176 MiB (cut 90112) and ~264 MiB (cut 45056)
+    ("slot-288MiB", _TRACED, 288 << 20, 28, [288 * _MiB, _TRACED], [288 * _MiB, 0],
+     [(0, 288 * _MiB, 90112, 90112), (288 * _MiB, _TRACED, 28672, 28672)]),
+    # (a slot above the file: one 352 MiB + 8 KiB slot, all of it the fine
+    # tail in 88 MiB pieces -- and a fifth piece of 4321 bytes, so there is a
+    # scan point at 352 MiB and the second share fires there, 4321 bytes
+    # before the end: this geometry never lost an ID)
+    ("slot-above-file", _TRACED, 1 << 30, 28,
+     [88 * _MiB, 176 * _MiB, 264 * _MiB, 352 * _MiB, _TRACED], [264 * _MiB, 352 * _MiB],
+     [(0, 264 * _MiB, 90112, 90112), (264 * _MiB, 352 * _MiB, 45056, 45056),
+      (352 * _MiB, _TRACED, 28672, 28672)]),
+    # round 6's advisor: 1 GiB through a 900 MiB slot at 12 feeder threads.
+    # The fine tail adds no scan point (900 MiB - 1 GiB is less than one
+    # 225 MiB piece), so the share at 768 MiB cannot fire
+    ("advisor-900MiB", 1 << 30, 900 << 20, 12, [900 * _MiB, 1 << 30], [900 * _MiB, 0],
+     [(0, 900 * _MiB, 262144, 0), (900 * _MiB, 1 << 30, 45056, 45056)]),
+    # the default slot: both shares fire, 32 MiB scan steps and the fine tail
+    ("default-slot", _TRACED, 32 << 20, 28, None, [192 * _MiB, 288 * _MiB],
+     [(0, 192 * _MiB, 90112, 90112), (192 * _MiB, 288 * _MiB, 45056, 45056),
+      (288 * _MiB, _TRACED, 28672, 28672)]),
+])
+def test_index_schedule_named(name, length, slot, threads, scan, fire, segs):
+    """Schedules pinned value by value.  Until round 7 a planned share that
+    could fire only at len had already given the feeder its cut while the last
+    digest used another: slot-288MiB and advisor-900MiB then lost the IDs of
+    the last segment's chunks between the two cuts ((28672, 45056] and
+    (45056, 131072]); slot-above-file and default-slot fire both shares."""
+    S = _index_sched()
+    s = S.schedule(_diag_lib(), length, slot, 1 << 30, threads)
+    assert S.violations(s, length) == []
+    if scan is not None:
+        assert s["scan"] == scan
+    assert [f for _, _, f in s["shares"]] == fire
+    assert s["segs"] == segs
+
+
+_ENV_CHILD = r"""
+import json, sys
+sys.path.insert(0, sys.argv[1])
+import index_sched as S
+lib = S.diag_lib()
+out = []
+for length, slot, window, threads in ((1 << 30, 32 << 20, 1 << 30, 12),
+                                      ((352 << 20) + 4321, 288 << 20, 1 << 30, 28),
+                                      ((640 << 20) + 4321, 32 << 20, 1 << 30, 28),
+                                      ((160 << 20) + 4321, 1 << 20, 80 << 20, 1)):
+    import ctypes
+    a, b = ctypes.c_uint64(), ctypes.c_uint64()
+    at, cut = (ctypes.c_uint64 * 8)(), (ctypes.c_uint64 * 8)()
+    n = lib.dsx_diag_index_plan(length, S.MAX, threads, ctypes.byref(a), ctypes.byref(b), at, cut, 8)
+    out.append([[a.value, b.value, list(at[:n]), list(cut[:n])], S.pieces(lib, length, slot, window),
+                S.schedule(lib, length, slot, window, threads)])
+print(json.dumps(out))
+"""
+
+
+@pytest.mark.parametrize("name", ["DSX_SHARE_NS", "DSX_SHARE_SLACK", "DSX_FINE_TAIL", "DSX_FINE_DIV"])
+def test_diag_env_defaults_are_the_librarys(name):
+    """_lib.DIAG_ENV lists, for each diagnostic setting, the value the
+    product library behaves as (loading the product library accepts that
+    value and refuses any other): the diagnostic library's plan, pieces and
+    schedule are the same with the variable unset and set to that value.
+    Each half in a fresh process (the environment is read at call time)."""
+    import json
+    import subprocess
+    import sys
+
+    from desync_amd import _lib
+    S = _index_sched()
+    _diag_lib()
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = []
+    for value in (None, _lib.DIAG_ENV[name]):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("DSX_")}
+        if value is not None:
+            env[name] = value
+        r = subprocess.run([sys.executable, "-c", _ENV_CHILD, here], env=env, capture_output=True,
+                           text=True, timeout=120, cwd=S.REPO)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out.append(json.loads(r.stdout))
+    assert out[0] == out[1], name
+    assert any(s["shares"] for _, _, s in out[0])  # (the cases reach what the settings shape)
