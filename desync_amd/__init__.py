@@ -13,6 +13,7 @@ mirror of the reference's Go API for that path:
     ChopFile, ChunkInvalid                                  (chop.go, errors.go)
     Index, IndexChunk, Index.WriteTo, IndexFromReader       (index.go)
     Digest (SHA512256 / SHA256), NullChunk                  (digest.go)
+    Info, IDSet, dedup (chunk-ID sets on the GPU)           (cmd/desync/info.go, fileseed.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
@@ -25,6 +26,7 @@ from .make import ChunkingStats, IndexFromFile, VerifyError, VerifyIndex, chunk_
     cut_fd, cut_host, file_size, ids_fd, ids_host, index_fd, index_host  # noqa: F401
 from .chop import ChopFile  # noqa: F401
 from .hash import Hash, NewHash  # noqa: F401
+from .info import IDSet, Info, dedup  # noqa: F401
 
 __all__ = [
     "ChunkerWindowSize", "Chunker", "ChunkerReadError", "NewChunker", "Params", "SHA256", "SHA512256", "NullChunk",
@@ -32,4 +34,5 @@ __all__ = [
     "IndexFromReader", "Chunk", "ChunkStorage", "ChunkStream", "MemoryStore", "ChunkingStats", "IndexFromFile", "cut_device", "cut_device_result",
     "cut_fd", "cut_host", "chunk_ids", "VerifyIndex", "VerifyError", "file_size", "index_fd",
     "index_host", "ids_fd", "ids_host", "ChopFile", "ChunkInvalid", "Hash", "NewHash",
+    "IDSet", "Info", "dedup",
 ]

@@ -58,12 +58,15 @@ EXPORTS = (
     "dsx_get_stats", "dsx_debug_trace", "dsx_index_fd", "dsx_index_host", "dsx_copy",
     "dsx_ids_fd", "dsx_ids_host", "dsx_progress", "dsx_shard_resolve_async", "dsx_shard_collect",
     "dsx_ctx_stream", "dsx_stamps_begin", "dsx_stamps_end", "dsx_host_copy",
-    "dsx_host_sha512_256",
+    "dsx_host_sha512_256", "dsx_idset_create", "dsx_idset_destroy", "dsx_idset_count", "dsx_dedup",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
 DSX_ENDS_DEVICE = 4
 DSX_HOST_SHA_SCALAR = 1
+DSX_IDS_DEVICE = 32
+DSX_SIZES = 64
+DSX_POS_NONE = 0xFFFFFFFF  # seed_pos of an ID the seed does not hold
 
 
 class Params(ctypes.Structure):
@@ -86,6 +89,13 @@ class Stats(ctypes.Structure):
         ("device_bytes", ctypes.c_uint64),
         ("host_tail_chunks", ctypes.c_uint64),
     ]
+
+
+class DedupTotals(ctypes.Structure):
+    """dsx_dedup_totals_t: the counters of info.go:135-185."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("total", "unique", "in_seed", "size", "size_not_in_seed")]
 
 
 class ScanStamp(ctypes.Structure):
@@ -232,6 +242,10 @@ def lib():
             "dsx_stamps_end": (i32, [vp, vp, u64, P(u64)]),
             "dsx_host_copy": (i32, [vp, vp, u64, i32]),
             "dsx_host_sha512_256": (i32, [vp, vp, u64, vp, i32, i32]),
+            "dsx_idset_create": (i32, [vp, vp, u64, u32, P(vp)]),
+            "dsx_idset_destroy": (i32, [vp, vp]),
+            "dsx_idset_count": (i32, [vp, P(u64), P(u64)]),
+            "dsx_dedup": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, P(DedupTotals), u32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)

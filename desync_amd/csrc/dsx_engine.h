@@ -89,6 +89,8 @@ struct DevBuf {
 }  // namespace dsx_host
 using namespace dsx_host;
 
+#include "dsx_idset.h"
+
 // A piece's candidate lists kept past its call (shards: the O(candidates)
 // re-walk re-runs only the stitch over them)
 struct KeptPiece {
@@ -327,6 +329,8 @@ struct dsx_ctx {
   DevBuf<uint32_t> idx_side_q;
   hipEvent_t q_ev[kQueueDepth] = {};
   uint32_t q_next = 0;
+
+  IdsetScratch idset;  // chunk-ID sets (dsx_idset.hip)
 };
 
 // Grow a device buffer; outstanding work may still use the old allocation, so

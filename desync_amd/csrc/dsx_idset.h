@@ -1,0 +1,39 @@
+// dsx_idset.h -- chunk-ID sets on the device (dsx_idset.hip): what a context
+// holds for them.  Included by dsx_engine.h behind DevBuf.
+#pragma once
+
+#include <stdint.h>
+
+#include <vector>
+
+struct dsx_ctx;
+
+// A set of chunk IDs (include/dsx.h, dsx_idset_t): a device copy of the IDs
+// and the open-addressing table built over them.  slots[s] is 0xFFFFFFFF
+// (empty) or the lowest position of one ID in ids[]; cap is a power of two
+// >= 2 n.  It belongs to the context that created it (its memory is counted
+// in that context's device_bytes and its kernels ran on that context's
+// stream) and dies with it.
+struct dsx_idset {
+  dsx_ctx* ctx = nullptr;
+  DevBuf<uint8_t> ids;     // n * 32 bytes
+  DevBuf<uint32_t> slots;  // cap words
+  uint64_t n = 0, n_unique = 0, cap = 0;
+  uint64_t salt = 0;       // hash key of this table
+};
+
+// dsx_dedup's scratch: the target's table, the staged copies of host (or
+// misaligned device) arguments, and the counters.  Grows once, reused.
+struct IdsetScratch {
+  DevBuf<uint32_t> slots;
+  DevBuf<uint8_t> ids;
+  DevBuf<uint64_t> ends;
+  DevBuf<uint32_t> first_pos, seed_pos;
+  DevBuf<unsigned long long> tot;  // kIdsetCounters words
+  std::vector<dsx_idset*> live;    // the context's sets
+};
+
+constexpr int kIdsetCounters = 4;  // unique, in_seed, size - start, size_not_in_seed
+
+uint64_t idset_device_bytes(const dsx_ctx* c);  // scratch + live sets
+void idset_release(dsx_ctx* c);                 // frees both (dsx_ctx_destroy)

@@ -415,6 +415,65 @@ int dsx_ids_fd(dsx_ctx_t *ctx, int fd, uint64_t off, uint64_t len, uint64_t star
 int dsx_ids_host(dsx_ctx_t *ctx, const void *h_blob, uint64_t len, uint64_t start,
                  const uint64_t *ends, uint64_t n, int algo, uint8_t *ids);
 
+/* ---- chunk-ID sets on the GPU: dedup, seed lookup, the info report ------------
+ * The set questions asked of a chunk list once its IDs exist: which chunks
+ * repeat inside the blob (the map of `desync info`, cmd/desync/info.go:135-150,
+ * and of the self seed, selfseed.go), which exist in a seed index and where
+ * (the `pos` map every FileSeed builds, fileseed.go:24-36: pos[id][0] is the
+ * first position), and how many bytes the seed does not cover
+ * (info.go:152-170).  The IDs stay in HBM, where dsx_chunk_ids(DSX_OUT_DEVICE)
+ * leaves them: a set is a lock-free open-addressing hash table over the
+ * 32-byte IDs, built and probed by kernels. */
+#define DSX_IDS_DEVICE 32u /* flag: ids[] is device memory (default: host) */
+#define DSX_SIZES 64u      /* flag: the ends[] argument holds chunk sizes, not end offsets */
+
+typedef struct dsx_idset dsx_idset_t; /* a set of chunk IDs resident on the ctx's device */
+/* Builds a set from n 32-byte IDs (host memory, or device memory with
+ * DSX_IDS_DEVICE; duplicates allowed; n == 0 gives an empty set).  The set
+ * keeps its own device copy of the IDs: the caller may free ids[] when the
+ * call returns.  Seeds from several indexes are concatenated by the caller
+ * (info.go:100-114 merges them into one map).  A set belongs to ctx: it is
+ * used with that context only, its memory counts in that context's
+ * device_bytes, and dsx_ctx_destroy frees the sets still alive.  Synchronous.
+ * n > 0xFFFFFFF0 or any other flag bit: DSX_E_INVAL. */
+int dsx_idset_create(dsx_ctx_t *ctx, const void *ids, uint64_t n, uint32_t flags,
+                     dsx_idset_t **out);
+int dsx_idset_destroy(dsx_ctx_t *ctx, dsx_idset_t *set);
+/* The number of IDs the set was built from and of distinct IDs among them. */
+int dsx_idset_count(const dsx_idset_t *set, uint64_t *n_ids, uint64_t *n_unique);
+
+/* The counters of info.go:135-185 (Total, Unique, InSeed, Size, SizeNotInSeed). */
+typedef struct dsx_dedup_totals {
+    uint64_t total;            /* n */
+    uint64_t unique;           /* first occurrences */
+    uint64_t in_seed;          /* first occurrences whose ID is in the seed */
+    uint64_t size;             /* ends[n-1]; with DSX_SIZES start + the sum of the sizes */
+    uint64_t size_not_in_seed; /* sum of the sizes of first occurrences not in the seed */
+} dsx_dedup_totals_t;
+
+/* Dedup of the n chunks [start, ends[0]), [ends[0], ends[1]), ... with the
+ * 32-byte IDs ids[] against themselves and, with seed non-NULL, against a
+ * seed set of the same context:
+ *   first_pos[i] = the lowest j <= i with ids[j] == ids[i]; chunk i is a first
+ *                  occurrence exactly when first_pos[i] == i;
+ *   seed_pos[i]  = the lowest position of that ID in the seed's ids[], or
+ *                  0xFFFFFFFF if the seed does not hold it (FileSeed's
+ *                  pos[id][0]); all 0xFFFFFFFF without a seed.
+ * Both are exact and the same on every run; either may be NULL.  totals
+ * (host memory, may be NULL) counts as info.go does: duplicates are counted
+ * once, at their first occurrence.  Chunk i's size is ends[i] - ends[i-1]
+ * (ends[0] - start), or ends[i] itself with DSX_SIZES (a hand-built list
+ * need not be contiguous).
+ * flags: DSX_IDS_DEVICE, DSX_ENDS_DEVICE, DSX_OUT_DEVICE (first_pos and
+ * seed_pos are device memory), DSX_SIZES; any other bit is DSX_E_INVAL.
+ * n == 0: zero totals, DSX_OK.  n > 0xFFFFFFF0: DSX_E_INVAL.  Host ends that
+ * decrease or begin below start: DSX_E_INVAL (dsx_last_error says which).  A
+ * seed of another context: DSX_E_INVAL.  Synchronous on the ctx stream; the
+ * table and the staged arguments live in the context (device_bytes). */
+int dsx_dedup(dsx_ctx_t *ctx, const void *ids, const uint64_t *ends, uint64_t start, uint64_t n,
+              const dsx_idset_t *seed, uint32_t *first_pos, uint32_t *seed_pos,
+              dsx_dedup_totals_t *totals, uint32_t flags);
+
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
     uint64_t chunks;            /* ChunksAccepted */
