@@ -14,6 +14,7 @@ mirror of the reference's Go API for that path:
     Index, IndexChunk, Index.WriteTo, IndexFromReader       (index.go)
     Digest (SHA512256 / SHA256), NullChunk                  (digest.go)
     Info, IDSet, dedup (chunk-ID sets on the GPU)           (cmd/desync/info.go, fileseed.go)
+    NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
@@ -27,6 +28,8 @@ from .make import ChunkingStats, IndexFromFile, VerifyError, VerifyIndex, chunk_
 from .chop import ChopFile  # noqa: F401
 from .hash import Hash, NewHash  # noqa: F401
 from .info import IDSet, Info, dedup  # noqa: F401
+from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
+    Segment  # noqa: F401
 
 __all__ = [
     "ChunkerWindowSize", "Chunker", "ChunkerReadError", "NewChunker", "Params", "SHA256", "SHA512256", "NullChunk",
@@ -35,4 +38,6 @@ __all__ = [
     "cut_fd", "cut_host", "chunk_ids", "VerifyIndex", "VerifyError", "file_size", "index_fd",
     "index_host", "ids_fd", "ids_host", "ChopFile", "ChunkInvalid", "Hash", "NewHash",
     "IDSet", "Info", "dedup",
+    "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
+    "AssembleBlob",
 ]

@@ -59,6 +59,7 @@ EXPORTS = (
     "dsx_ids_fd", "dsx_ids_host", "dsx_progress", "dsx_shard_resolve_async", "dsx_shard_collect",
     "dsx_ctx_stream", "dsx_stamps_begin", "dsx_stamps_end", "dsx_host_copy",
     "dsx_host_sha512_256", "dsx_idset_create", "dsx_idset_destroy", "dsx_idset_count", "dsx_dedup",
+    "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -67,6 +68,11 @@ DSX_HOST_SHA_SCALAR = 1
 DSX_IDS_DEVICE = 32
 DSX_SIZES = 64
 DSX_POS_NONE = 0xFFFFFFFF  # seed_pos of an ID the seed does not hold
+DSX_SRC_NULL = -1          # dsx_plan_seg_t.source: the null seed
+DSX_SRC_STORE = -2         # ... the packed store buffer
+DSX_STORE_DEVICE = 128
+DSX_ASSEMBLE_UNALIGNED = 256
+DSX_ASSEMBLE_TILE = 65536
 
 
 class Params(ctypes.Structure):
@@ -96,6 +102,31 @@ class DedupTotals(ctypes.Structure):
 
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("total", "unique", "in_seed", "size", "size_not_in_seed")]
+
+
+class PlanSeg(ctypes.Structure):
+    """dsx_plan_seg_t: one plan entry (a SeedSegmentCandidate, sequencer.go:21-25)."""
+
+    _fields_ = [
+        ("dst_off", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("src_off", ctypes.c_uint64),
+        ("first", ctypes.c_uint32), ("count", ctypes.c_uint32),
+        ("source", ctypes.c_int32), ("seed_first", ctypes.c_uint32),
+    ]
+
+
+class PlanTotals(ctypes.Structure):
+    """dsx_plan_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("segments", "seed_chunks", "seed_bytes", "null_chunks", "null_bytes",
+                 "store_chunks", "store_bytes", "store_unique", "store_len")]
+
+
+class PlanSeed(ctypes.Structure):
+    """dsx_plan_seed_t: one seed of dsx_plan_walk, as classes."""
+
+    _fields_ = [("tclass", ctypes.c_void_p), ("sclass", ctypes.c_void_p),
+                ("ends", ctypes.c_void_p), ("m", ctypes.c_uint64)]
 
 
 class ScanStamp(ctypes.Structure):
@@ -246,6 +277,11 @@ def lib():
             "dsx_idset_destroy": (i32, [vp, vp]),
             "dsx_idset_count": (i32, [vp, P(u64), P(u64)]),
             "dsx_dedup": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, P(DedupTotals), u32]),
+            "dsx_plan_walk": (i32, [vp, u64, u64, vp, vp, vp, u32, u32, vp, u64, vp, u64,
+                                    P(PlanTotals)]),
+            "dsx_seed_plan": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, vp, u32, vp, u64, vp, u64,
+                                    P(PlanTotals), u32]),
+            "dsx_assemble": (i32, [vp, vp, u64, vp, vp, u32, vp, u64, vp, u64, u32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)

@@ -1,0 +1,267 @@
+// dsx_assemble.hip -- AssembleFile's data path (assemble.go:93-309) for blobs
+// resident in HBM: one kernel gathers a plan's segments (unaligned,
+// variable-length byte ranges of several seed blobs and of the packed store
+// buffer, or zeros) into the output blob.
+//
+// Work is divided by output bytes, not by segments: a workgroup owns one tile
+// of DSX_ASSEMBLE_TILE bytes of the output (tiles are cut on 16-byte aligned
+// ADDRESSES of the output), finds the segment that holds the tile's first
+// byte by binary search over the ascending dst_off, and walks on from there.
+// One 256 KiB chunk and one 1 GiB run load the device alike.
+//
+// Each (segment ∩ tile) is written as a head of up to 15 single bytes up to
+// the next 16-byte address of the output, a body of aligned 16-byte stores,
+// and a tail of up to 15 single bytes.  Every store covers only bytes of its
+// own piece: no granule is read back and merged, and no byte is written
+// twice, so two segments (of two workgroups) that meet inside one granule
+// never see each other.
+//
+// The source of a body word sits at an arbitrary byte offset from it (chunk
+// starts are arbitrary).  Two forms of that load are built and were measured
+// (DESIGN.md 4.6 has both rates): two aligned 16-byte loads combined by a byte
+// shift (the product's, the faster by a little), and, with
+// DSX_ASSEMBLE_UNALIGNED, one unaligned 16-byte global load.  The shift form
+// reads whole aligned granules, which at the first and the last word of a
+// piece would reach up to 15 bytes outside the source range: those two words
+// are loaded unaligned in either form, so no byte outside a source range is
+// ever read.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "dsx_engine.h"
+
+namespace dsx {
+
+typedef unsigned long long u64;
+constexpr int kAsmThreads = 256;
+constexpr u64 kAsmTile = DSX_ASSEMBLE_TILE;
+static_assert(kAsmTile % (16 * kAsmThreads) == 0, "a tile is whole passes of the workgroup");
+
+struct AsmSeg {
+  u64 dst_off, bytes;
+  const uint8_t* src;  // null: zeros
+};
+static_assert(sizeof(AsmSeg) == 24, "three words a segment (IdsetScratch::asm_segs)");
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef v4u v4u_unaligned __attribute__((aligned(1)));
+// The sources are device memory (hipMalloc'd blobs); their pointers come out of
+// the segment table, so say so, or the loads are flat ones.
+#define DSX_GLOBAL __attribute__((address_space(1)))
+typedef const DSX_GLOBAL uint8_t* gsrc_t;
+
+// the 16 source bytes at s (any alignment)
+template <bool SHIFT>
+__device__ __forceinline__ uint4 load16(gsrc_t s) {
+  if (!SHIFT) {
+    const v4u v = *(const DSX_GLOBAL v4u_unaligned*)s;
+    return make_uint4(v.x, v.y, v.z, v.w);
+  }
+  const uint32_t mis = (uint32_t)((uintptr_t)s & 15);
+  const DSX_GLOBAL v4u* a = (const DSX_GLOBAL v4u*)(s - mis);
+  const v4u lo = a[0];
+  if (mis == 0) return make_uint4(lo.x, lo.y, lo.z, lo.w);
+  const v4u hi = a[1];
+  const uint32_t r = mis & 3;
+  uint32_t d0, d1, d2, d3, d4;
+  switch (mis >> 2) {  // (uniform over a piece)
+    case 0: d0 = lo.x, d1 = lo.y, d2 = lo.z, d3 = lo.w, d4 = hi.x; break;
+    case 1: d0 = lo.y, d1 = lo.z, d2 = lo.w, d3 = hi.x, d4 = hi.y; break;
+    case 2: d0 = lo.z, d1 = lo.w, d2 = hi.x, d3 = hi.y, d4 = hi.z; break;
+    default: d0 = lo.w, d1 = hi.x, d2 = hi.y, d3 = hi.z, d4 = hi.w; break;
+  }
+  // ({high, low} >> 8 r), low word
+  return make_uint4(__builtin_amdgcn_alignbyte(d1, d0, r), __builtin_amdgcn_alignbyte(d2, d1, r),
+                    __builtin_amdgcn_alignbyte(d3, d2, r), __builtin_amdgcn_alignbyte(d4, d3, r));
+}
+
+// the workgroup copies len bytes to dst from src (null: zeros)
+template <bool SHIFT>
+__device__ __forceinline__ void copy_piece(uint8_t* dst, gsrc_t src, u64 len) {
+  const uint32_t tid = threadIdx.x;
+  const u64 head = std::min<u64>(len, (16 - ((uintptr_t)dst & 15)) & 15);
+  const u64 nw = (len - head) >> 4;
+  const u64 tail = (len - head) & 15;
+  if (tid < head) dst[tid] = src ? src[tid] : 0;
+  if (tid >= 64 && tid - 64 < tail) {  // (another wave than the head's)
+    const u64 i = head + 16 * nw + (tid - 64);
+    dst[i] = src ? src[i] : 0;
+  }
+  uint4* d = reinterpret_cast<uint4*>(dst + head);
+  u64 w = tid;
+  if (!src) {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    for (; w < nw; w += kAsmThreads) d[w] = z;
+    return;
+  }
+  gsrc_t s = src + head;
+  // word i of the body; the granules of the shift form lie inside [s, s + 16 nw)
+  // for every word but the first and the last
+  auto load = [&](u64 i) {
+    return (SHIFT && i != 0 && i + 1 != nw) ? load16<true>(s + 16 * i) : load16<false>(s + 16 * i);
+  };
+  for (; w + 3 * kAsmThreads < nw; w += 4 * kAsmThreads) {  // four loads in flight per lane
+    const uint4 v0 = load(w);
+    const uint4 v1 = load(w + kAsmThreads);
+    const uint4 v2 = load(w + 2 * kAsmThreads);
+    const uint4 v3 = load(w + 3 * kAsmThreads);
+    d[w] = v0;
+    d[w + kAsmThreads] = v1;
+    d[w + 2 * kAsmThreads] = v2;
+    d[w + 3 * kAsmThreads] = v3;
+  }
+  if (w < nw) {  // the last, partial round: still every load before the first store
+    const u64 w1 = w + kAsmThreads, w2 = w + 2 * kAsmThreads;
+    uint4 v0 = load(w), v1 = v0, v2 = v0;
+    if (w1 < nw) v1 = load(w1);
+    if (w2 < nw) v2 = load(w2);
+    d[w] = v0;
+    if (w1 < nw) d[w1] = v1;
+    if (w2 < nw) d[w2] = v2;
+  }
+}
+
+// Tile k covers the output addresses [A + k T, A + (k + 1) T), A = out rounded
+// down to 16 bytes (skew = out - A), clipped to [out, out + out_len).
+template <bool SHIFT>
+__global__ __launch_bounds__(kAsmThreads) void assemble_kernel(const AsmSeg* segs, u64 nsegs,
+                                                               uint8_t* out, u64 out_len, u64 skew,
+                                                               u64 tile0) {
+  const u64 k = tile0 + blockIdx.x;
+  const u64 lo = k * kAsmTile > skew ? k * kAsmTile - skew : 0;
+  const u64 hi = std::min<u64>((k + 1) * kAsmTile - skew, out_len);
+  if (lo >= hi) return;
+  // the first segment that ends behind lo (segment ends ascend with dst_off)
+  u64 l = 0, r = nsegs;
+  while (l < r) {
+    const u64 m = (l + r) >> 1;
+    if (segs[m].dst_off + segs[m].bytes <= lo) l = m + 1;
+    else r = m;
+  }
+  for (u64 j = l; j < nsegs; ++j) {
+    const AsmSeg s = segs[j];
+    if (s.dst_off >= hi) break;
+    const u64 b = std::max<u64>(s.dst_off, lo), e = std::min<u64>(s.dst_off + s.bytes, hi);
+    if (b < e) copy_piece<SHIFT>(out + b, s.src ? (gsrc_t)s.src + (b - s.dst_off) : nullptr, e - b);
+  }
+}
+
+}  // namespace dsx
+
+using namespace dsx;
+
+namespace {
+
+int seg_error(dsx_ctx* c, uint64_t i, const char* what) {
+  c->err = "segment " + std::to_string(i) + ": " + what;
+  return DSX_E_INVAL;
+}
+
+// [a, a + an) and [b, b + bn) share a byte
+bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return an && bn && x < y + bn && y < x + an;
+}
+
+}  // namespace
+
+extern "C" int dsx_assemble(dsx_ctx_t* c, const dsx_plan_seg_t* segs, uint64_t nsegs,
+                            const void* const* d_seeds, const uint64_t* seed_lens, uint32_t nseeds,
+                            const void* store, uint64_t store_len, void* d_out, uint64_t out_len,
+                            uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  const uint32_t f_store = DSX_STORE_DEVICE, f_unal = DSX_ASSEMBLE_UNALIGNED;
+  if (!c || (flags & ~(f_store | f_unal)) != 0) return DSX_E_INVAL;
+  if ((nsegs && !segs) || (out_len && !d_out) || (store_len && !store)) return DSX_E_INVAL;
+  if (nseeds && (!d_seeds || !seed_lens)) return DSX_E_INVAL;
+  if (out_len > UINT64_MAX - (uintptr_t)d_out) return DSX_E_INVAL;
+  c->err.clear();
+  // ---- every check comes before any launch -----------------------------------
+  for (uint32_t k = 0; k < nseeds; ++k) {
+    if (seed_lens[k] && !d_seeds[k]) return DSX_E_INVAL;
+    if (overlaps(d_out, out_len, d_seeds[k], seed_lens[k])) {
+      c->err = "the output overlaps seed " + std::to_string(k);
+      return DSX_E_INVAL;
+    }
+  }
+  if ((flags & f_store) && overlaps(d_out, out_len, store, store_len)) {
+    c->err = "the output overlaps the store buffer";
+    return DSX_E_INVAL;
+  }
+  try {
+    std::vector<AsmSeg> dev;
+    dev.reserve(nsegs);
+    const bool store_dev = (flags & f_store) != 0;
+    uint64_t prev_end = 0;
+    for (uint64_t i = 0; i < nsegs; ++i) {
+      const dsx_plan_seg_t& g = segs[i];
+      if (g.dst_off < prev_end) return seg_error(c, i, "dst_off is below the end of the segment before it");
+      if (g.bytes > out_len || g.dst_off > out_len - g.bytes)
+        return seg_error(c, i, "dst_off + bytes is beyond the output");
+      uint64_t src_len = 0;
+      const uint8_t* base = nullptr;
+      if (g.source >= 0) {
+        if ((uint32_t)g.source >= nseeds) return seg_error(c, i, "source names no seed");
+        src_len = seed_lens[g.source];
+        base = (const uint8_t*)d_seeds[g.source];
+      } else if (g.source == DSX_SRC_STORE) {
+        src_len = store_len;
+        base = (const uint8_t*)store;  // (host store bytes: rebased below, once staged)
+      } else if (g.source != DSX_SRC_NULL) {
+        return seg_error(c, i, "source is neither a seed, the null seed nor the store");
+      }
+      if (g.source != DSX_SRC_NULL && (g.bytes > src_len || g.src_off > src_len - g.bytes))
+        return seg_error(c, i, "src_off + bytes is beyond its source");
+      prev_end = g.dst_off + g.bytes;
+      if (!g.bytes) continue;
+      AsmSeg a;
+      a.dst_off = g.dst_off;
+      a.bytes = g.bytes;
+      a.src = g.source == DSX_SRC_NULL ? nullptr : base + g.src_off;
+      if (g.source == DSX_SRC_STORE && !store_dev) a.src = (const uint8_t*)(uintptr_t)g.src_off;
+      dev.push_back(a);
+    }
+    if (dev.empty()) return DSX_OK;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    IdsetScratch& t = c->idset;
+    hipStream_t st = c->stream;
+    if (!store_dev && store_len) {
+      HIPCHK(c, grow(c, t.asm_store, store_len));
+      HIPCHK(c, hipMemcpyAsync(t.asm_store.p, store, store_len, hipMemcpyHostToDevice, st));
+      uint64_t k = 0;
+      for (uint64_t i = 0; i < nsegs; ++i) {
+        if (!segs[i].bytes) continue;
+        if (segs[i].source == DSX_SRC_STORE) dev[k].src = t.asm_store.p + segs[i].src_off;
+        ++k;
+      }
+    }
+    HIPCHK(c, grow(c, t.asm_segs, 3 * dev.size()));
+    HIPCHK(c, hipMemcpyAsync(t.asm_segs.p, dev.data(), dev.size() * sizeof(AsmSeg),
+                             hipMemcpyHostToDevice, st));
+    const uint64_t skew = (uintptr_t)d_out & 15;
+    const uint64_t tile0 = (dev.front().dst_off + skew) / kAsmTile;
+    const uint64_t tile1 = (dev.back().dst_off + dev.back().bytes + skew + kAsmTile - 1) / kAsmTile;
+    const AsmSeg* d_segs = reinterpret_cast<const AsmSeg*>(t.asm_segs.p);
+    // (a grid's x dimension holds 2^31 - 1 workgroups: 128 TiB of output a launch)
+    for (uint64_t k0 = tile0; k0 < tile1;) {
+      const uint64_t nb = std::min<uint64_t>(tile1 - k0, 1u << 30);
+      if (!(flags & f_unal))
+        hipLaunchKernelGGL(assemble_kernel<true>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
+                           d_segs, (u64)dev.size(), (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
+      else
+        hipLaunchKernelGGL(assemble_kernel<false>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
+                           d_segs, (u64)dev.size(), (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
+      HIPCHK(c, hipGetLastError());
+      k0 += nb;
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    return DSX_OK;
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
+}

@@ -20,6 +20,10 @@ struct dsx_idset {
   DevBuf<uint32_t> slots;  // cap words
   uint64_t n = 0, n_unique = 0, cap = 0;
   uint64_t salt = 0;       // hash key of this table
+  // the seed's own classes (dsx_seed_plan): sclass[p] = the lowest position of
+  // ids[p]'s ID, built by the first plan that uses the set and kept
+  DevBuf<uint32_t> sclass;         // n words, or empty
+  std::vector<uint32_t> h_sclass;  // its host copy
 };
 
 // dsx_dedup's scratch: the target's table, the staged copies of host (or
@@ -31,6 +35,10 @@ struct IdsetScratch {
   DevBuf<uint32_t> first_pos, seed_pos;
   DevBuf<unsigned long long> tot;  // kIdsetCounters words
   std::vector<dsx_idset*> live;    // the context's sets
+  // the read side (dsx_seed_plan, dsx_assemble: dsx_assemble.hip)
+  DevBuf<uint8_t> is_null;         // one byte per target chunk
+  DevBuf<uint64_t> asm_segs;       // the plan as the gather kernel reads it (3 words a segment)
+  DevBuf<uint8_t> asm_store;       // the staged copy of host store bytes
 };
 
 constexpr int kIdsetCounters = 4;  // unique, in_seed, size - start, size_not_in_seed

@@ -19,6 +19,7 @@
 // unkeyed one) would let a crafted index line every ID up behind one slot.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <atomic>
@@ -162,6 +163,18 @@ __global__ __launch_bounds__(kIdsetThreads) void idset_probe_kernel(ProbeArgs a)
   }
 }
 
+// dsx_seed_plan's classes: cls[i] = the lowest position in the seed of ids[i]'s
+// ID (kEmpty: not held); with is_null non-null, also whether ids[i] is null_id.
+__global__ __launch_bounds__(kIdsetThreads) void idset_class_kernel(
+    const uint8_t* ids, u64 n, const uint8_t* seed_ids, const uint32_t* seed_slots, u64 seed_n,
+    u64 seed_mask, u64 seed_salt, uint32_t* cls, Id32 null_id, uint8_t* is_null) {
+  const u64 i = (u64)blockIdx.x * kIdsetThreads + threadIdx.x;
+  if (i >= n) return;
+  const Id32 me = load_id(ids, i);
+  if (cls) cls[i] = idset_find(seed_ids, seed_n, seed_slots, seed_mask, seed_salt, me);
+  if (is_null) is_null[i] = same_id(me, null_id) ? 1 : 0;
+}
+
 }  // namespace dsx
 
 using namespace dsx;
@@ -207,6 +220,7 @@ int enqueue_build(dsx_ctx* c, const uint8_t* d_ids, uint64_t n, uint32_t* slots,
 void free_set(dsx_idset* s) {
   s->ids.release();
   s->slots.release();
+  s->sclass.release();
   delete s;
 }
 
@@ -215,15 +229,15 @@ void free_set(dsx_idset* s) {
 uint64_t idset_device_bytes(const dsx_ctx* c) {
   const IdsetScratch& t = c->idset;
   uint64_t b = t.slots.n * 4 + t.ids.n + t.ends.n * 8 + t.first_pos.n * 4 + t.seed_pos.n * 4 +
-               t.tot.n * 8;
-  for (const dsx_idset* s : t.live) b += s->ids.n + s->slots.n * 4;
+               t.tot.n * 8 + t.is_null.n + t.asm_segs.n * 8 + t.asm_store.n;
+  for (const dsx_idset* s : t.live) b += s->ids.n + s->slots.n * 4 + s->sclass.n * 4;
   return b;
 }
 
 void idset_release(dsx_ctx* c) {
   IdsetScratch& t = c->idset;
   t.slots.release(), t.ids.release(), t.ends.release(), t.first_pos.release(), t.seed_pos.release();
-  t.tot.release();
+  t.tot.release(), t.is_null.release(), t.asm_segs.release(), t.asm_store.release();
   for (dsx_idset* s : t.live) free_set(s);
   t.live.clear();
 }
@@ -389,4 +403,105 @@ extern "C" int dsx_dedup(dsx_ctx_t* c, const void* ids, const uint64_t* ends, ui
     totals->size_not_in_seed = tot[3];
   }
   return DSX_OK;
+}
+
+// ---- the plan from IDs (SeedSequencer.Plan, sequencer.go:41-74) ----------------
+// The classes dsx_plan_walk needs are what the tables already answer: a seed's
+// table probed with the target's IDs gives tclass, probed with the seed's own
+// IDs sclass (kept in the set), and dsx_dedup first_pos.  They cross to the
+// host as 4 bytes per chunk per seed; the walk itself is host code.
+extern "C" int dsx_seed_plan(dsx_ctx_t* c, const void* ids, const uint64_t* ends, uint64_t start,
+                             uint64_t n, dsx_idset_t* const* seeds,
+                             const uint64_t* const* seed_ends, const uint64_t* seed_counts,
+                             uint32_t nseeds, const uint8_t* null_id, uint32_t limit,
+                             dsx_plan_seg_t* segs, uint64_t seg_cap, uint32_t* store_chunks,
+                             uint64_t store_cap, dsx_plan_totals_t* totals, uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_ends = DSX_ENDS_DEVICE;
+  if (!c || !totals || (flags & ~(f_ids | f_ends)) != 0) return DSX_E_INVAL;
+  if (n > kIdsetMaxN || (n && (!ids || !ends))) return DSX_E_INVAL;
+  if (nseeds && (!seeds || !seed_ends || !seed_counts)) return DSX_E_INVAL;
+  *totals = dsx_plan_totals_t{};
+  IdsetScratch& t = c->idset;
+  for (uint32_t k = 0; k < nseeds; ++k) {
+    dsx_idset* s = seeds[k];
+    if (!s || std::find(t.live.begin(), t.live.end(), s) == t.live.end()) {
+      c->err = "seed " + std::to_string(k) + " is not a set of this context";
+      return DSX_E_INVAL;
+    }
+    if (seed_counts[k] != s->n || (s->n && !seed_ends[k])) {
+      c->err = "seed " + std::to_string(k) + ": the number of chunk ends differs from the set's IDs";
+      return DSX_E_INVAL;
+    }
+  }
+  if (n == 0) return DSX_OK;
+  try {
+    std::vector<uint32_t> first_pos(n);
+    int rc = dsx_dedup(c, ids, ends, start, n, nullptr, first_pos.data(), nullptr, nullptr, flags);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    // (dsx_dedup staged the IDs it could not read in place; they are still there)
+    const uint8_t* d_ids = (const uint8_t*)ids;
+    if (!(flags & f_ids) || !aligned(ids, 16)) d_ids = t.ids.p;
+    std::vector<uint64_t> h_ends;
+    if (flags & f_ends) {
+      h_ends.resize(n);
+      HIPCHK(c, hipMemcpyAsync(h_ends.data(), ends, n * 8, hipMemcpyDeviceToHost, st));
+      ends = h_ends.data();
+    }
+    Id32 nid{};
+    if (null_id) memcpy(&nid, null_id, 32);
+    auto classes = [&](const uint8_t* of, uint64_t cnt, const dsx_idset* s, uint32_t* cls,
+                       uint8_t* isn) -> int {
+      const uint32_t blocks = (uint32_t)((cnt + kIdsetThreads - 1) / kIdsetThreads);
+      hipLaunchKernelGGL(idset_class_kernel, dim3(blocks), dim3(kIdsetThreads), 0, st, of, (u64)cnt,
+                         s ? s->ids.p : nullptr, s ? s->slots.p : nullptr, (u64)(s ? s->n : 0),
+                         (u64)(s ? s->cap - 1 : 0), (u64)(s ? s->salt : 0), cls, nid, isn);
+      HIPCHK(c, hipGetLastError());
+      return DSX_OK;
+    };
+    // each seed's own classes, once per set
+    for (uint32_t k = 0; k < nseeds; ++k) {
+      dsx_idset* s = seeds[k];
+      if (!s->n || s->h_sclass.size() == s->n) continue;
+      HIPCHK(c, s->sclass.ensure(s->n));
+      if ((rc = classes(s->ids.p, s->n, s, s->sclass.p, nullptr))) return rc;
+      std::vector<uint32_t> h(s->n);
+      HIPCHK(c, hipMemcpyAsync(h.data(), s->sclass.p, s->n * 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      s->h_sclass.swap(h);
+    }
+    std::vector<uint8_t> is_null;
+    if (null_id) {
+      is_null.resize(n);
+      HIPCHK(c, grow(c, t.is_null, n));
+    }
+    HIPCHK(c, grow(c, t.seed_pos, n));
+    std::vector<std::vector<uint32_t>> tcls(nseeds);
+    for (uint32_t k = 0; k < nseeds || (k == 0 && null_id); ++k) {
+      uint8_t* isn = (k == 0 && null_id) ? t.is_null.p : nullptr;
+      const dsx_idset* s = k < nseeds ? seeds[k] : nullptr;
+      if ((rc = classes(d_ids, n, s, s ? t.seed_pos.p : nullptr, isn))) return rc;
+      if (s) {
+        tcls[k].resize(n);
+        HIPCHK(c, hipMemcpyAsync(tcls[k].data(), t.seed_pos.p, n * 4, hipMemcpyDeviceToHost, st));
+      }
+      if (isn) HIPCHK(c, hipMemcpyAsync(is_null.data(), isn, n, hipMemcpyDeviceToHost, st));
+      // (the next seed's launch overwrites seed_pos: the copy is stream-ordered before it)
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    std::vector<dsx_plan_seed_t> ps(nseeds);
+    for (uint32_t k = 0; k < nseeds; ++k) {
+      ps[k].tclass = tcls[k].data();
+      ps[k].sclass = seeds[k]->h_sclass.data();
+      ps[k].ends = seed_ends[k];
+      ps[k].m = seeds[k]->n;
+    }
+    rc = dsx_plan_walk(ends, start, n, first_pos.data(), null_id ? is_null.data() : nullptr,
+                       ps.data(), nseeds, limit, segs, seg_cap, store_chunks, store_cap, totals);
+    if (rc == DSX_E_INVAL) c->err = "the chunk lists are not well formed (ends that decrease)";
+    return rc;
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
 }

@@ -105,6 +105,14 @@ class MemoryStore:
         with self._lock:
             self.chunks[chunk.ID()] = data
 
+    def GetChunk(self, cid: bytes) -> bytes:
+        """Store.GetChunk (store.go): the uncompressed bytes of a chunk."""
+        with self._lock:
+            try:
+                return self.chunks[cid]
+            except KeyError:
+                raise KeyError(f"chunk {bytes(cid).hex()} missing from store") from None
+
 
 _BATCH = 64  # chunks per hand-off to the store workers
 _READ_AHEAD = 256 << 20  # two of dsx_stream_ids' 128 MiB batches

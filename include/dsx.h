@@ -21,6 +21,11 @@
  *                           chunks its range, then seams are aligned from a
  *                           small all-gathered seam record (syncWith,
  *                           make.go:277-327)
+ *   dsx_seed_plan        <- SeedSequencer.Plan, sequencer.go:41-74 (FileSeed /
+ *                           nullChunkSeed LongestMatchWith, fileseed.go:42-80,
+ *                           nullseed.go:45-74)
+ *   dsx_assemble         <- AssembleFile's copy of the plan's segments,
+ *                           assemble.go:93-309, for blobs resident in HBM
  *
  * Conventions (cgo-safe): plain pointers and sizes only; no pointer passed in
  * is retained after a call returns; every function returns 0 or a negative
@@ -473,6 +478,130 @@ typedef struct dsx_dedup_totals {
 int dsx_dedup(dsx_ctx_t *ctx, const void *ids, const uint64_t *ends, uint64_t start, uint64_t n,
               const dsx_idset_t *seed, uint32_t *first_pos, uint32_t *seed_pos,
               dsx_dedup_totals_t *totals, uint32_t flags);
+
+/* ---- seed plans and in-HBM assembly: the read side (desync extract) -----------
+ * SeedSequencer.Plan (sequencer.go:41-74) walks the target index and takes, at
+ * each position, the longest run of consecutive chunks some seed holds
+ * (FileSeed.LongestMatchWith fileseed.go:42-80, maxMatchFrom :114-136;
+ * nullChunkSeed.LongestMatchWith nullseed.go:45-74); AssembleFile
+ * (assemble.go:93-309) copies those runs out of the seed blobs and fills the
+ * rest from the store.  Here the plan is a list of plain segments and the
+ * assembly one gather kernel over blobs resident in HBM. */
+#define DSX_SRC_NULL (-1)   /* segment source: the null seed (zeros) */
+#define DSX_SRC_STORE (-2)  /* segment source: the packed store buffer */
+#define DSX_STORE_DEVICE 128u /* dsx_assemble flag: the store bytes are device memory */
+#define DSX_ASSEMBLE_UNALIGNED 256u /* dsx_assemble flag (measurement, tools/assemble_rate.py): load
+                                   each misaligned source word with one unaligned load instead of two
+                                   aligned loads and a byte shift; the same bytes are written */
+#define DSX_ASSEMBLE_TILE 65536u /* output bytes one workgroup of the gather kernel owns */
+
+/* One plan entry (a SeedSegmentCandidate, sequencer.go:21-25). */
+typedef struct dsx_plan_seg {
+    uint64_t dst_off;    /* offset of target chunk `first` in the target (start included) */
+    uint64_t bytes;      /* the target bytes the segment covers */
+    uint64_t src_off;    /* seed: offset of chunk seed_first in the seed blob; store: offset of
+                            the chunk in the packed store buffer; null: 0 */
+    uint32_t first;      /* target chunks [first, first + count) */
+    uint32_t count;
+    int32_t source;      /* seed number >= 0, DSX_SRC_NULL or DSX_SRC_STORE */
+    uint32_t seed_first; /* position of the first matching chunk in the seed, else 0xFFFFFFFF */
+} dsx_plan_seg_t;
+
+typedef struct dsx_plan_totals {
+    uint64_t segments;
+    uint64_t seed_chunks, seed_bytes;   /* from file seeds */
+    uint64_t null_chunks, null_bytes;   /* from the null seed */
+    uint64_t store_chunks, store_bytes; /* store segments (one chunk each), repeats included */
+    uint64_t store_unique;              /* distinct store chunks: the length of store_chunks[] */
+    uint64_t store_len;                 /* length of the packed store buffer */
+} dsx_plan_totals_t;
+
+/* One seed of dsx_plan_walk, as 32-bit classes (two IDs are equal exactly when
+ * their classes are): tclass[i] is the lowest position in this seed of target
+ * chunk i's ID or 0xFFFFFFFF (dsx_dedup's seed_pos), sclass[p] the lowest
+ * position in this seed of seed chunk p's ID (the seed's own first_pos),
+ * ends[m] the seed's chunk ends (its first chunk starts at 0). */
+typedef struct dsx_plan_seed {
+    const uint32_t *tclass; /* n words */
+    const uint32_t *sclass; /* m words */
+    const uint64_t *ends;   /* m words */
+    uint64_t m;
+} dsx_plan_seed_t;
+
+/* SeedSequencer.Plan over classes.  Host code: no context, no GPU.
+ * ends/start/n and first_pos[n] as in dsx_dedup; is_null[n] (may be NULL: no
+ * null seed) is one byte per chunk, set where the chunk's ID is the null
+ * chunk's; limit caps the chunks of one seed match (0: none; the reference
+ * uses 100 when it cannot reflink, fileseed.go:62-68).
+ * Per seed, the match at target position cur is the maximum, over every seed
+ * position p of class tclass[cur] in ascending order, of the number of
+ * consecutive positions matching from (cur, p), replaced only by a strictly
+ * greater length (ties go to the lowest p).  Between seeds
+ * (SeedSequencer.Next, sequencer.go:56-74): the null seed first
+ * (assemble.go:151-158), then the file seeds in the order given; a seed
+ * replaces the choice only with strictly more bytes, a file seed's bytes being
+ * the seed's own (fileseed.go:156-162) and the null seed's the target's; with
+ * no match the segment is one chunk from the store.
+ * The packed store buffer holds each distinct store chunk once, in the order
+ * of its first occurrence in the target; a repeated store chunk gets the
+ * src_off of the first (the effect of selfseed.go without a write-after-write
+ * dependency in the output).  store_chunks[] receives the target positions of
+ * the distinct store chunks in buffer order: the fetch list.
+ * If seg_cap or store_cap is too small: DSX_E_CAPACITY, with totals->segments
+ * and totals->store_unique the required counts (the totals are complete).
+ * Crafted arrays never index out of bounds; DSX_E_INVAL for an sclass[p] > p
+ * or not a fixed point (sclass[sclass[p]] != sclass[p]), a tclass[i] neither
+ * < m nor 0xFFFFFFFF or not a fixed point of sclass, first_pos[i] > i, ends
+ * that decrease, n or m > 0xFFFFFFF0.
+ * Cost: only the positions the sequencer visits are matched.  Runs of one ID
+ * are stepped over a run at a time on both sides, and of the positions inside
+ * one seed run only the two that can win are tried, so a sparse image (one
+ * long run of the null chunk's ID in target and seed) costs work proportional
+ * to its runs.  Adversarial periodic inputs (ABAB... in target and seed) have
+ * runs of one chunk and stay as expensive as in the reference: every
+ * occurrence is tried and every match walked chunk by chunk. */
+int dsx_plan_walk(const uint64_t *ends, uint64_t start, uint64_t n, const uint32_t *first_pos,
+                  const uint8_t *is_null, const dsx_plan_seed_t *seeds, uint32_t nseeds,
+                  uint32_t limit, dsx_plan_seg_t *segs, uint64_t seg_cap, uint32_t *store_chunks,
+                  uint64_t store_cap, dsx_plan_totals_t *totals);
+
+/* The plan from IDs: ids/ends/start/n as in dsx_dedup (flags DSX_IDS_DEVICE,
+ * DSX_ENDS_DEVICE; any other bit is DSX_E_INVAL); seeds[nseeds] are sets of
+ * this context built from each seed index's IDs in order (NewIndexSeed,
+ * fileseed.go:24-36), seed_ends[k] the host chunk ends of seed k and
+ * seed_counts[k] their number, which must equal the set's dsx_idset_count
+ * (else DSX_E_INVAL, as for a seed of another context); null_id is the 32-byte
+ * ID of the null chunk (nullseed.go:31) or NULL for no null seed.  The classes
+ * are made on the device by the sets' tables (a set keeps its own sclass once
+ * built, counted in device_bytes), copied to the host (4 bytes per chunk per
+ * seed) and walked by dsx_plan_walk, whose outputs (host memory) and return
+ * codes these are.  n == 0: zero segments, DSX_OK.  Synchronous. */
+int dsx_seed_plan(dsx_ctx_t *ctx, const void *ids, const uint64_t *ends, uint64_t start,
+                  uint64_t n, dsx_idset_t *const *seeds, const uint64_t *const *seed_ends,
+                  const uint64_t *seed_counts, uint32_t nseeds, const uint8_t *null_id,
+                  uint32_t limit, dsx_plan_seg_t *segs, uint64_t seg_cap, uint32_t *store_chunks,
+                  uint64_t store_cap, dsx_plan_totals_t *totals, uint32_t flags);
+
+/* AssembleFile's data path (assemble.go:93-309) for blobs in HBM: gathers the
+ * nsegs segments (host memory) into d_out[0..out_len): segment s writes
+ * d_out[dst_off, dst_off + bytes) from d_seeds[source] + src_off, from the
+ * packed store bytes + src_off (host memory, staged through the context; device
+ * memory with DSX_STORE_DEVICE), or as zeros (DSX_SRC_NULL).  Output bytes no
+ * segment covers are left untouched.  One kernel, work divided by output bytes
+ * (DSX_ASSEMBLE_TILE per workgroup) so one chunk and one 1 GiB run load the
+ * device alike.  Synchronous on the ctx stream.
+ * Checked on the host before any launch, each DSX_E_INVAL with a
+ * dsx_last_error text naming the segment: segments ascending and
+ * non-overlapping in dst_off; dst_off + bytes <= out_len; src_off + bytes
+ * within the source's length; source < nseeds or one of the two constants;
+ * [d_out, d_out + out_len) overlapping no source.  With these the kernel
+ * cannot read or write outside the buffers it was given, whatever the plan
+ * says.  Flags: DSX_STORE_DEVICE, DSX_ASSEMBLE_UNALIGNED; any other bit:
+ * DSX_E_INVAL. */
+int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
+                 const void *const *d_seeds, const uint64_t *seed_lens, uint32_t nseeds,
+                 const void *store, uint64_t store_len, void *d_out, uint64_t out_len,
+                 uint32_t flags);
 
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
