@@ -15,12 +15,13 @@ mirror of the reference's Go API for that path:
     Digest (SHA512256 / SHA256), NullChunk                  (digest.go)
     Info, IDSet, dedup (chunk-ID sets on the GPU)           (cmd/desync/info.go, fileseed.go)
     NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
+    DeviceStore, ChopBlob, ChunkMissing (a chunk store in HBM)  (store.go, local.go, chop.go, errors.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
 from .chunker import ChunkerReadError, ChunkerWindowSize, Chunker, NewChunker, Params  # noqa: F401
 from .digest import SHA256, SHA512256, NewNullChunk, NullChunk, set_digest  # noqa: F401
-from .errors import ChunkInvalid, Interrupted  # noqa: F401
+from .errors import ChunkInvalid, ChunkMissing, Interrupted  # noqa: F401
 from .index import FormatIndex, Index, IndexChunk, IndexFromReader  # noqa: F401
 from .stream import Chunk, ChunkStorage, ChunkStream, MemoryStore  # noqa: F401
 from .make import ChunkingStats, IndexFromFile, VerifyError, VerifyIndex, chunk_ids, cut_device, cut_device_result, \
@@ -30,6 +31,7 @@ from .hash import Hash, NewHash  # noqa: F401
 from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
     Segment  # noqa: F401
+from .store import ChopBlob, DeviceStore  # noqa: F401
 
 __all__ = [
     "ChunkerWindowSize", "Chunker", "ChunkerReadError", "NewChunker", "Params", "SHA256", "SHA512256", "NullChunk",
@@ -39,5 +41,5 @@ __all__ = [
     "index_host", "ids_fd", "ids_host", "ChopFile", "ChunkInvalid", "Hash", "NewHash",
     "IDSet", "Info", "dedup",
     "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
-    "AssembleBlob",
+    "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing",
 ]

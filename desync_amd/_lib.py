@@ -59,7 +59,9 @@ EXPORTS = (
     "dsx_ids_fd", "dsx_ids_host", "dsx_progress", "dsx_shard_resolve_async", "dsx_shard_collect",
     "dsx_ctx_stream", "dsx_stamps_begin", "dsx_stamps_end", "dsx_host_copy",
     "dsx_host_sha512_256", "dsx_idset_create", "dsx_idset_destroy", "dsx_idset_count", "dsx_dedup",
-    "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble",
+    "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble", "dsx_store_create", "dsx_store_destroy",
+    "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
+    "dsx_store_resolve", "dsx_store_verify",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -120,6 +122,19 @@ class PlanTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("segments", "seed_chunks", "seed_bytes", "null_chunks", "null_bytes",
                  "store_chunks", "store_bytes", "store_unique", "store_len")]
+
+
+class StoreCounts(ctypes.Structure):
+    """dsx_store_counts_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in ("chunks", "bytes", "max_chunks", "arena_bytes")]
+
+
+class StorePutTotals(ctypes.Structure):
+    """dsx_store_put_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("total", "stored", "stored_bytes", "present", "repeats")]
 
 
 class PlanSeed(ctypes.Structure):
@@ -282,6 +297,15 @@ def lib():
             "dsx_seed_plan": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, vp, u32, vp, u64, vp, u64,
                                     P(PlanTotals), u32]),
             "dsx_assemble": (i32, [vp, vp, u64, vp, vp, u32, vp, u64, vp, u64, u32]),
+            "dsx_store_create": (i32, [vp, u64, u64, P(vp)]),
+            "dsx_store_destroy": (i32, [vp, vp]),
+            "dsx_store_count": (i32, [vp, P(StoreCounts)]),
+            "dsx_store_put": (i32, [vp, vp, vp, u64, vp, vp, u64, u64, P(StorePutTotals), u32]),
+            "dsx_store_locate": (i32, [vp, vp, vp, u64, vp, vp, P(u64), u32]),
+            "dsx_store_arena": (i32, [vp, P(vp), P(u64)]),
+            "dsx_store_entries": (i32, [vp, vp, u64, u64, vp, vp, u32]),
+            "dsx_store_resolve": (i32, [vp, vp, vp, u64, vp, u64, P(u64), P(u64), P(u32), u32]),
+            "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)

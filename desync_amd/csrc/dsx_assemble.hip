@@ -41,12 +41,6 @@ constexpr int kAsmThreads = 256;
 constexpr u64 kAsmTile = DSX_ASSEMBLE_TILE;
 static_assert(kAsmTile % (16 * kAsmThreads) == 0, "a tile is whole passes of the workgroup");
 
-struct AsmSeg {
-  u64 dst_off, bytes;
-  const uint8_t* src;  // null: zeros
-};
-static_assert(sizeof(AsmSeg) == 24, "three words a segment (IdsetScratch::asm_segs)");
-
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef v4u v4u_unaligned __attribute__((aligned(1)));
 // The sources are device memory (hipMalloc'd blobs); their pointers come out of
@@ -169,6 +163,28 @@ bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
 
 }  // namespace
 
+int assemble_launch(dsx_ctx* c, const AsmSeg* d_segs, uint64_t nsegs, void* d_out, uint64_t out_len,
+                    uint64_t lo, uint64_t hi, bool unaligned) {
+  if (!nsegs || lo >= hi) return DSX_OK;
+  hipStream_t st = c->stream;
+  const uint64_t skew = (uintptr_t)d_out & 15;
+  const uint64_t tile0 = (lo + skew) / kAsmTile;
+  const uint64_t tile1 = (hi + skew + kAsmTile - 1) / kAsmTile;
+  // (a grid's x dimension holds 2^31 - 1 workgroups: 128 TiB of output a launch)
+  for (uint64_t k0 = tile0; k0 < tile1;) {
+    const uint64_t nb = std::min<uint64_t>(tile1 - k0, 1u << 30);
+    if (!unaligned)
+      hipLaunchKernelGGL(assemble_kernel<true>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
+                         d_segs, (u64)nsegs, (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
+    else
+      hipLaunchKernelGGL(assemble_kernel<false>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
+                         d_segs, (u64)nsegs, (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
+    HIPCHK(c, hipGetLastError());
+    k0 += nb;
+  }
+  return DSX_OK;
+}
+
 extern "C" int dsx_assemble(dsx_ctx_t* c, const dsx_plan_seg_t* segs, uint64_t nsegs,
                             const void* const* d_seeds, const uint64_t* seed_lens, uint32_t nseeds,
                             const void* store, uint64_t store_len, void* d_out, uint64_t out_len,
@@ -243,22 +259,10 @@ extern "C" int dsx_assemble(dsx_ctx_t* c, const dsx_plan_seg_t* segs, uint64_t n
     HIPCHK(c, grow(c, t.asm_segs, 3 * dev.size()));
     HIPCHK(c, hipMemcpyAsync(t.asm_segs.p, dev.data(), dev.size() * sizeof(AsmSeg),
                              hipMemcpyHostToDevice, st));
-    const uint64_t skew = (uintptr_t)d_out & 15;
-    const uint64_t tile0 = (dev.front().dst_off + skew) / kAsmTile;
-    const uint64_t tile1 = (dev.back().dst_off + dev.back().bytes + skew + kAsmTile - 1) / kAsmTile;
     const AsmSeg* d_segs = reinterpret_cast<const AsmSeg*>(t.asm_segs.p);
-    // (a grid's x dimension holds 2^31 - 1 workgroups: 128 TiB of output a launch)
-    for (uint64_t k0 = tile0; k0 < tile1;) {
-      const uint64_t nb = std::min<uint64_t>(tile1 - k0, 1u << 30);
-      if (!(flags & f_unal))
-        hipLaunchKernelGGL(assemble_kernel<true>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
-                           d_segs, (u64)dev.size(), (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
-      else
-        hipLaunchKernelGGL(assemble_kernel<false>, dim3((uint32_t)nb), dim3(kAsmThreads), 0, st,
-                           d_segs, (u64)dev.size(), (uint8_t*)d_out, (u64)out_len, (u64)skew, (u64)k0);
-      HIPCHK(c, hipGetLastError());
-      k0 += nb;
-    }
+    const int rc = assemble_launch(c, d_segs, dev.size(), d_out, out_len, dev.front().dst_off,
+                                   dev.back().dst_off + dev.back().bytes, (flags & f_unal) != 0);
+    if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(st));
     return DSX_OK;
   } catch (const std::bad_alloc&) {

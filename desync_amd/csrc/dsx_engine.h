@@ -90,6 +90,7 @@ struct DevBuf {
 using namespace dsx_host;
 
 #include "dsx_idset.h"
+#include "dsx_store.h"
 
 // A piece's candidate lists kept past its call (shards: the O(candidates)
 // re-walk re-runs only the stitch over them)
@@ -331,6 +332,7 @@ struct dsx_ctx {
   uint32_t q_next = 0;
 
   IdsetScratch idset;  // chunk-ID sets (dsx_idset.hip)
+  StoreScratch store;  // chunk stores (dsx_store.hip)
 };
 
 // Grow a device buffer; outstanding work may still use the old allocation, so

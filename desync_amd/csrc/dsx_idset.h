@@ -41,6 +41,21 @@ struct IdsetScratch {
   DevBuf<uint8_t> asm_store;       // the staged copy of host store bytes
 };
 
+// One segment as the gather kernel reads it (dsx_assemble.hip).
+namespace dsx {
+struct AsmSeg {
+  unsigned long long dst_off, bytes;
+  const uint8_t* src;  // null: zeros
+};
+static_assert(sizeof(AsmSeg) == 24, "three words a segment (IdsetScratch::asm_segs)");
+}  // namespace dsx
+// Enqueues assemble_kernel on the ctx stream over a segment table that is
+// already on the device (ascending, non-overlapping dst_off), for the bytes
+// [lo, hi) of d_out[0, out_len): the tiles that hold them.  No check, no wait:
+// the caller has made both.
+int assemble_launch(dsx_ctx* c, const dsx::AsmSeg* d_segs, uint64_t nsegs, void* d_out,
+                    uint64_t out_len, uint64_t lo, uint64_t hi, bool unaligned);
+
 constexpr int kIdsetCounters = 4;  // unique, in_seed, size - start, size_not_in_seed
 
 uint64_t idset_device_bytes(const dsx_ctx* c);  // scratch + live sets

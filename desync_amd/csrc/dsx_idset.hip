@@ -17,6 +17,9 @@
 // The hash mixes all four 64-bit words of the ID with a per-table key: IDs
 // come from index files and can be crafted, and a prefix hash (or a public
 // unkeyed one) would let a crafted index line every ID up behind one slot.
+//
+// The device side of the table (the ID loads, the hash, the lookup) is in
+// dsx_idset_dev.h: the chunk store (dsx_store.hip) keeps the same table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -26,51 +29,9 @@
 #include <random>
 
 #include "dsx_engine.h"
+#include "dsx_idset_dev.h"
 
 namespace dsx {
-
-typedef unsigned long long u64;
-constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-constexpr int kIdsetThreads = 256;
-
-struct Id32 {
-  uint4 lo, hi;
-};
-
-__device__ __forceinline__ Id32 load_id(const uint8_t* ids, u64 i) {
-  const uint4* p = reinterpret_cast<const uint4*>(ids + 32 * i);  // (ids is 16-byte aligned)
-  Id32 r;
-  r.lo = p[0];
-  r.hi = p[1];
-  return r;
-}
-
-__device__ __forceinline__ bool same_id(const Id32& a, const Id32& b) {
-  const uint32_t d = (a.lo.x ^ b.lo.x) | (a.lo.y ^ b.lo.y) | (a.lo.z ^ b.lo.z) | (a.lo.w ^ b.lo.w) |
-                     (a.hi.x ^ b.hi.x) | (a.hi.y ^ b.hi.y) | (a.hi.z ^ b.hi.z) | (a.hi.w ^ b.hi.w);
-  return d == 0;
-}
-
-__device__ __forceinline__ u64 mix64(u64 x) {
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-// every step is a bijection of the word it takes in: two IDs that differ in
-// one word never share a hash before the mask
-__device__ __forceinline__ u64 hash_id(const Id32& a, u64 salt) {
-  u64 h = mix64(salt ^ ((u64)a.lo.y << 32 | a.lo.x));
-  h = mix64(h ^ ((u64)a.lo.w << 32 | a.lo.z));
-  h = mix64(h ^ ((u64)a.hi.y << 32 | a.hi.x));
-  return mix64(h ^ ((u64)a.hi.w << 32 | a.hi.z));
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;  // (lane 0 holds the wave's sum)
-}
 
 // One lane per ID.  *claimed counts the slots taken: the distinct IDs.
 __global__ __launch_bounds__(kIdsetThreads) void idset_insert_kernel(const uint8_t* ids, u64 n,
@@ -105,17 +66,6 @@ __global__ __launch_bounds__(kIdsetThreads) void idset_insert_kernel(const uint8
   }
   const u64 b = __ballot(took);
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(claimed, (u64)__popcll(b));
-}
-
-__device__ __forceinline__ uint32_t idset_find(const uint8_t* ids, u64 n, const uint32_t* slots,
-                                               u64 mask, u64 salt, const Id32& key) {
-  u64 s = hash_id(key, salt) & mask;
-  for (u64 step = 0; step <= mask; ++step, s = (s + 1) & mask) {
-    const uint32_t j = slots[s];
-    if (j == kEmpty) return kEmpty;
-    if (j < n && same_id(load_id(ids, j), key)) return j;
-  }
-  return kEmpty;
 }
 
 struct ProbeArgs {
@@ -179,18 +129,14 @@ __global__ __launch_bounds__(kIdsetThreads) void idset_class_kernel(
 
 using namespace dsx;
 
-namespace {
-
-constexpr uint64_t kIdsetMaxN = 0xFFFFFFF0ull;
-
-uint64_t table_cap(uint64_t n) {
+uint64_t idset_table_cap(uint64_t n) {
   uint64_t cap = 16;
   while (cap < 2 * n) cap <<= 1;
   return cap;
 }
 
 // a fresh hash key per table (splitmix64 of a counter from a random origin)
-uint64_t next_salt() {
+uint64_t idset_next_salt() {
   static std::atomic<uint64_t> ctr{[] {
     std::random_device rd;
     return ((uint64_t)rd() << 32) ^ rd();
@@ -201,12 +147,10 @@ uint64_t next_salt() {
   return z ^ (z >> 31);
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // clears the table and the counters, then inserts ids[0..n) (device, 16-byte
 // aligned); *tot[0] ends as the number of distinct IDs
-int enqueue_build(dsx_ctx* c, const uint8_t* d_ids, uint64_t n, uint32_t* slots, uint64_t cap,
-                  uint64_t salt, u64* tot) {
+int idset_enqueue_build(dsx_ctx* c, const uint8_t* d_ids, uint64_t n, uint32_t* slots, uint64_t cap,
+                        uint64_t salt, u64* tot) {
   HIPCHK(c, hipMemsetAsync(slots, 0xFF, cap * sizeof(uint32_t), c->stream));
   HIPCHK(c, hipMemsetAsync(tot, 0, kIdsetCounters * sizeof(u64), c->stream));
   if (!n) return DSX_OK;
@@ -216,6 +160,12 @@ int enqueue_build(dsx_ctx* c, const uint8_t* d_ids, uint64_t n, uint32_t* slots,
   HIPCHK(c, hipGetLastError());
   return DSX_OK;
 }
+
+namespace {
+
+constexpr uint64_t kIdsetMaxN = 0xFFFFFFF0ull;
+
+inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 void free_set(dsx_idset* s) {
   s->ids.release();
@@ -254,8 +204,8 @@ extern "C" int dsx_idset_create(dsx_ctx_t* c, const void* ids, uint64_t n, uint3
   dsx_idset* s = new dsx_idset;
   s->ctx = c;
   s->n = n;
-  s->cap = table_cap(n);
-  s->salt = next_salt();
+  s->cap = idset_table_cap(n);
+  s->salt = idset_next_salt();
   int rc = DSX_OK;
   auto build = [&]() -> int {
     HIPCHK(c, s->ids.ensure(n * 32));
@@ -263,7 +213,7 @@ extern "C" int dsx_idset_create(dsx_ctx_t* c, const void* ids, uint64_t n, uint3
     HIPCHK(c, t.tot.ensure(kIdsetCounters));
     const hipMemcpyKind kind = (flags & known) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (n) HIPCHK(c, hipMemcpyAsync(s->ids.p, ids, n * 32, kind, c->stream));
-    const int r = enqueue_build(c, s->ids.p, n, s->slots.p, s->cap, s->salt, t.tot.p);
+    const int r = idset_enqueue_build(c, s->ids.p, n, s->slots.p, s->cap, s->salt, t.tot.p);
     if (r) return r;
     u64 uniq = 0;
     HIPCHK(c, hipMemcpyAsync(&uniq, t.tot.p, sizeof uniq, hipMemcpyDeviceToHost, c->stream));
@@ -355,11 +305,11 @@ extern "C" int dsx_dedup(dsx_ctx_t* c, const void* ids, const uint64_t* ends, ui
     HIPCHK(c, grow(c, t.seed_pos, n));
     d_seed = t.seed_pos.p;
   }
-  const uint64_t cap = table_cap(n);
+  const uint64_t cap = idset_table_cap(n);
   HIPCHK(c, grow(c, t.slots, cap));
   HIPCHK(c, grow(c, t.tot, kIdsetCounters));
-  const uint64_t salt = next_salt();
-  int rc = enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  const uint64_t salt = idset_next_salt();
+  int rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
   if (rc) return rc;
   // (the insert left the distinct count in tot[0]; the probe counts it again
   // from first_pos, so start it from zero)

@@ -1,0 +1,653 @@
+// dsx_store.hip -- a chunk store in HBM (store.go:21-33, local.go,
+// chunkstorage.go): an append-only, deduplicating arena of chunk bytes keyed
+// by chunk ID, filled from a resident blob without a host round trip per
+// chunk and read in place by dsx_assemble.  The counterpart of a LocalStore
+// with Uncompressed: true (store.go:98-99).
+//
+// Layout (dsx_store.h): entry e is the e-th chunk appended; ids[32 e] is its
+// ID, arena[ends[e-1], ends[e]) its bytes.  The ID table is dsx_idset.hip's,
+// with entry numbers for positions: a full slot never changes.  Capacity is
+// fixed at creation, so the arena's address is stable and dsx_assemble can be
+// handed it as the store buffer.
+//
+// A put is a fixed sequence of launches on the context's stream:
+//   select  the call's own table (idset_insert_kernel), then one lane per
+//           chunk: new[i] = first occurrence in this call and not in the
+//           store; the same kernel validates the chunk ends, reduces the
+//           totals and leaves {new chunks, new bytes} per workgroup;
+//   scan    one workgroup turns those pairs into exclusive prefix sums;
+//   (the host reads the totals and the error word, and accepts the capacity)
+//   append  each new chunk takes entry chunks + rank and arena offset bytes +
+//           prefix (its rank inside the workgroup by ballot and popcount, its
+//           byte offset by wave shuffles and LDS), writes its ID, its end and
+//           a gather record, and claims a table slot;
+//   copy    assemble_kernel over the gather records into arena[used, used +
+//           stored_bytes): tiles are cut over the destination.
+// The IDs appended in one call differ from each other and from every ID the
+// store holds (that is what select selected).  The insert therefore claims
+// the first empty slot on its probe sequence and compares no ID: a comparison
+// would read an entry another lane of the same launch is still writing.
+// No lane waits for another; the probe loops are bounded by the capacity.
+//
+// Out of scope: removing chunks, prune and compaction; growing a store;
+// compression and encryption converters; persistence (dsx_store_entries plus
+// the arena are enough for a caller to save and reload one); use from a
+// second context or GPU.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "dsx_engine.h"
+#include "dsx_idset_dev.h"
+
+namespace dsx {
+
+constexpr int kStoreThreads = 256;
+constexpr int kStoreWaves = kStoreThreads / 64;
+
+struct PutArgs {
+  const uint8_t* ids;    // the call's IDs
+  const uint64_t* ends;  // chunk ends
+  u64 start, n, len;
+  const uint8_t* blob;
+  const uint32_t* slots;  // the call's own table (built by the launch before)
+  u64 mask, salt;
+  uint8_t* st_ids;  // the store
+  uint64_t* st_ends;
+  uint32_t* st_slots;
+  u64 st_n, st_mask, st_salt, st_bytes;
+  uint8_t* flag;  // new[i]
+  u64* blk;       // {chunks, bytes} per workgroup
+  u64* tot;       // [kStoreCounters]
+  AsmSeg* segs;   // [n_new], written by the append
+  u64 n_new;      // the accepted total: the append's ranks stay below it
+};
+
+// inclusive prefix sum over the wave's lanes
+__device__ __forceinline__ u64 wave_scan(u64 v) {
+  const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 t = __shfl_up(v, o, 64);
+    if (lane >= (uint32_t)o) v += t;
+  }
+  return v;
+}
+
+// One lane per chunk.  A chunk whose end lies below its start or beyond the
+// blob sets the error word (the host then stops before the append).
+__global__ __launch_bounds__(kStoreThreads) void store_select_kernel(PutArgs a) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool is_new = false, present = false, bad = false;
+  u64 size = 0;
+  if (i < a.n) {
+    const u64 e = a.ends[i], prev = i ? a.ends[i - 1] : a.start;
+    bad = e < prev || e > a.len;
+    const Id32 me = load_id(a.ids, i);
+    if (idset_find(a.ids, a.n, a.slots, a.mask, a.salt, me) == (uint32_t)i) {
+      present = idset_find(a.st_ids, a.st_n, a.st_slots, a.st_mask, a.st_salt, me) != kEmpty;
+      is_new = !present;
+    }
+    if (is_new && !bad) size = e - prev;
+    a.flag[i] = is_new ? 1 : 0;
+  }
+  const u64 bn = __ballot(is_new), bp = __ballot(present), bb = __ballot(bad);
+  const u64 bytes = wave_sum(size);
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    if (bn) atomicAdd(&a.tot[0], (u64)__popcll(bn));
+    if (bytes) atomicAdd(&a.tot[1], bytes);
+    if (bp) atomicAdd(&a.tot[2], (u64)__popcll(bp));
+    if (bb) atomicOr(&a.tot[3], 1ull);
+    w_cnt[wave] = (u64)__popcll(bn);
+    w_bytes[wave] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 cnt = 0, by = 0;
+#pragma unroll
+    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
+    a.blk[2 * (u64)blockIdx.x] = cnt;
+    a.blk[2 * (u64)blockIdx.x + 1] = by;
+  }
+}
+
+// One workgroup: the workgroups' {chunks, bytes} pairs become their exclusive
+// prefix sums, kStoreThreads pairs a pass with a carry between passes.
+__global__ __launch_bounds__(kStoreThreads) void store_scan_kernel(u64* blk, u64 nblk) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  u64 carry_c = 0, carry_b = 0;
+  for (u64 base = 0; base < nblk; base += kStoreThreads) {
+    const u64 j = base + threadIdx.x;
+    const u64 c = j < nblk ? blk[2 * j] : 0, b = j < nblk ? blk[2 * j + 1] : 0;
+    const u64 ic = wave_scan(c), ib = wave_scan(b);
+    if (lane == 63) w_cnt[wave] = ic, w_bytes[wave] = ib;
+    __syncthreads();
+    u64 off_c = 0, off_b = 0, all_c = 0, all_b = 0;
+#pragma unroll
+    for (int w = 0; w < kStoreWaves; ++w) {
+      if ((uint32_t)w < wave) off_c += w_cnt[w], off_b += w_bytes[w];
+      all_c += w_cnt[w], all_b += w_bytes[w];
+    }
+    if (j < nblk) {
+      blk[2 * j] = carry_c + off_c + ic - c;
+      blk[2 * j + 1] = carry_b + off_b + ib - b;
+    }
+    carry_c += all_c, carry_b += all_b;
+    __syncthreads();  // (the next pass writes the wave totals again)
+  }
+}
+
+// One lane per chunk, the grid of store_select_kernel.  Runs only after the
+// host has accepted the capacity: entry numbers stay below max_chunks and the
+// table keeps an empty slot (load factor <= 0.5).
+__global__ __launch_bounds__(kStoreThreads) void store_append_kernel(PutArgs a) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  bool is_new = false;
+  u64 size = 0, prev = 0;
+  if (i < a.n && a.flag[i]) {
+    is_new = true;
+    const u64 e = a.ends[i];
+    prev = i ? a.ends[i - 1] : a.start;
+    if (prev <= e && e <= a.len) size = e - prev;  // (select checked it: never reads past the blob)
+  }
+  const u64 bn = __ballot(is_new);
+  const u64 ib = wave_scan(size);
+  if (lane == 63) w_cnt[wave] = (u64)__popcll(bn), w_bytes[wave] = ib;
+  __syncthreads();
+  if (!is_new) return;
+  u64 rank = a.blk[2 * (u64)blockIdx.x] + (u64)__popcll(bn & ((1ull << lane) - 1));
+  u64 off = a.blk[2 * (u64)blockIdx.x + 1] + ib - size;
+#pragma unroll
+  for (int w = 0; w < kStoreWaves; ++w)
+    if ((uint32_t)w < wave) rank += w_cnt[w], off += w_bytes[w];
+  if (rank >= a.n_new) return;  // (never: the ranks are the scan of the flags the total counted)
+  const u64 e = a.st_n + rank;
+  off += a.st_bytes;
+  const Id32 me = load_id(a.ids, i);
+  uint4* dst = reinterpret_cast<uint4*>(a.st_ids + 32 * e);
+  dst[0] = me.lo;
+  dst[1] = me.hi;
+  a.st_ends[e] = off + size;
+  AsmSeg g;
+  g.dst_off = off;
+  g.bytes = size;
+  g.src = a.blob + prev;
+  a.segs[rank] = g;
+  // the first empty slot on the probe sequence; no ID is compared (see above)
+  u64 s = hash_id(me, a.st_salt) & a.st_mask;
+  for (u64 step = 0; step <= a.st_mask; ++step, s = (s + 1) & a.st_mask) {
+    uint32_t cur = __hip_atomic_load(&a.st_slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur != kEmpty) continue;
+    cur = atomicCAS(&a.st_slots[s], kEmpty, (uint32_t)e);
+    if (cur == kEmpty) break;
+  }
+}
+
+// One lane per question: ids[idx ? idx[i] : i] looked up in the store.
+__global__ __launch_bounds__(kStoreThreads) void store_lookup_kernel(
+    const uint8_t* ids, const uint32_t* idx, u64 n, const uint8_t* st_ids, const uint64_t* st_ends,
+    const uint32_t* st_slots, u64 st_n, u64 st_mask, u64 st_salt, uint64_t* offs, uint64_t* sizes,
+    u64* missing) {
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool miss = false;
+  if (i < n) {
+    const Id32 key = load_id(ids, idx ? idx[i] : i);
+    const uint32_t e = idset_find(st_ids, st_n, st_slots, st_mask, st_salt, key);
+    miss = e == kEmpty;
+    const u64 lo = miss ? UINT64_MAX : (e ? st_ends[e - 1] : 0);
+    if (offs) offs[i] = lo;
+    if (sizes) sizes[i] = miss ? 0 : st_ends[e] - lo;
+  }
+  const u64 bm = __ballot(miss);
+  if ((threadIdx.x & 63) == 0 && bm) atomicAdd(missing, (u64)__popcll(bm));
+}
+
+// flag[e] = the computed ID of entry e differs from the stored one
+__global__ __launch_bounds__(kStoreThreads) void store_compare_kernel(const uint8_t* got,
+                                                                      const uint8_t* want, u64 n,
+                                                                      uint8_t* flag, u64* n_bad) {
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool bad = false;
+  if (i < n) {
+    bad = !same_id(load_id(got, i), load_id(want, i));
+    flag[i] = bad ? 1 : 0;
+  }
+  const u64 bb = __ballot(bad);
+  if ((threadIdx.x & 63) == 0 && bb) atomicAdd(n_bad, (u64)__popcll(bb));
+}
+
+}  // namespace dsx
+
+using namespace dsx;
+
+namespace {
+
+constexpr uint64_t kStoreMaxN = 0xFFFFFFF0ull;
+
+inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kStoreThreads - 1) / kStoreThreads); }
+
+int invalid(dsx_ctx* c, const char* what) {
+  c->err = what;
+  return DSX_E_INVAL;
+}
+
+// [a, a + an) and [b, b + bn) share a byte
+bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return an && bn && x < y + bn && y < x + an;
+}
+
+bool owns(const dsx_ctx* c, const dsx_store* s) {
+  const auto& live = c->store.live;
+  return std::find(live.begin(), live.end(), s) != live.end();
+}
+
+void free_store(dsx_store* s) {
+  s->ids.release();
+  s->ends.release();
+  s->slots.release();
+  s->arena.release();
+  delete s;
+}
+
+// the IDs where a kernel can read them: in place, or staged in the context
+int stage_ids(dsx_ctx* c, const void* ids, uint64_t n, bool device, const uint8_t** out) {
+  *out = (const uint8_t*)ids;
+  if (device && aligned(ids, 16)) return DSX_OK;
+  IdsetScratch& t = c->idset;
+  HIPCHK(c, grow(c, t.ids, n * 32));
+  HIPCHK(c, hipMemcpyAsync(t.ids.p, ids, n * 32, hipMemcpyDefault, c->stream));
+  *out = t.ids.p;
+  return DSX_OK;
+}
+
+}  // namespace
+
+uint64_t store_device_bytes(const dsx_ctx* c) {
+  const StoreScratch& t = c->store;
+  uint64_t b = t.flag.n + t.blk.n * 8 + t.tot.n * 8 + t.segs.n * 8 + t.offs.n * 8 + t.sizes.n * 8 +
+               t.idx.n * 4 + t.vids.n;
+  for (const dsx_store* s : t.live) b += s->ids.n + s->ends.n * 8 + s->slots.n * 4 + s->arena.n;
+  return b;
+}
+
+void store_release(dsx_ctx* c) {
+  StoreScratch& t = c->store;
+  t.flag.release(), t.blk.release(), t.tot.release(), t.segs.release(), t.offs.release();
+  t.sizes.release(), t.idx.release(), t.vids.release();
+  for (dsx_store* s : t.live) free_store(s);
+  t.live.clear();
+}
+
+extern "C" int dsx_store_create(dsx_ctx_t* c, uint64_t arena_bytes, uint64_t max_chunks,
+                                dsx_store_t** out) {
+  DSX_FLUSH_BEHIND(c);
+  if (!c || !out || max_chunks > kStoreMaxN) return DSX_E_INVAL;
+  *out = nullptr;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  dsx_store* s = new dsx_store;
+  s->ctx = c;
+  s->max_chunks = max_chunks;
+  s->arena_bytes = arena_bytes;
+  s->cap = idset_table_cap(max_chunks);
+  s->salt = idset_next_salt();
+  auto build = [&]() -> int {
+    HIPCHK(c, s->ids.ensure(max_chunks * 32));
+    HIPCHK(c, s->ends.ensure(max_chunks));
+    HIPCHK(c, s->slots.ensure(s->cap));
+    HIPCHK(c, s->arena.ensure(arena_bytes));
+    HIPCHK(c, hipMemsetAsync(s->slots.p, 0xFF, s->cap * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSX_OK;
+  };
+  const int rc = build();
+  if (rc) {
+    (void)hipStreamSynchronize(c->stream);
+    free_store(s);
+    return rc == DSX_E_HIP ? DSX_E_NOMEM : rc;
+  }
+  c->store.live.push_back(s);
+  *out = s;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_destroy(dsx_ctx_t* c, dsx_store_t* s) {
+  if (!c || !s) return DSX_E_INVAL;
+  auto& live = c->store.live;
+  auto it = std::find(live.begin(), live.end(), s);
+  if (it == live.end()) return invalid(c, "the store belongs to another context");
+  live.erase(it);
+  HIPCHK(c, hipSetDevice(c->device));
+  (void)hipStreamSynchronize(c->stream);
+  free_store(s);
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_count(const dsx_store_t* s, dsx_store_counts_t* out) {
+  if (!s || !out) return DSX_E_INVAL;
+  out->chunks = s->chunks;
+  out->bytes = s->bytes;
+  out->max_chunks = s->max_chunks;
+  out->arena_bytes = s->arena_bytes;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_arena(const dsx_store_t* s, const void** d_arena, uint64_t* used) {
+  if (!s) return DSX_E_INVAL;
+  if (d_arena) *d_arena = s->arena.p;
+  if (used) *used = s->bytes;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, uint64_t len,
+                             const void* ids, const uint64_t* ends, uint64_t start, uint64_t n,
+                             dsx_store_put_totals_t* totals, uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_ends = DSX_ENDS_DEVICE;
+  if (!c || !s) return DSX_E_INVAL;
+  if (totals) *totals = dsx_store_put_totals_t{};
+  if ((flags & ~(f_ids | f_ends)) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (n > kStoreMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
+  if (n && (!ids || !ends)) return invalid(c, "the IDs or the chunk ends are missing");
+  if (len && !d_blob) return invalid(c, "the blob is missing");
+  if (len > UINT64_MAX - (uintptr_t)d_blob) return invalid(c, "the blob wraps the address space");
+  if (n == 0) return DSX_OK;
+  if (overlaps(d_blob, len, s->arena.p, s->arena_bytes))
+    return invalid(c, "the blob overlaps the store's arena");
+  if (!(flags & f_ends)) {
+    uint64_t prev = start;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (ends[i] < prev || ends[i] > len)
+        return invalid(c, "chunk ends must be non-decreasing, start <= ends[0], ends[n-1] <= len");
+      prev = ends[i];
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  IdsetScratch& t = c->idset;
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+
+  const uint8_t* d_ids = nullptr;
+  int rc = stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  if (rc) return rc;
+  const uint64_t* d_ends = ends;
+  if (!(flags & f_ends) || !aligned(ends, 8)) {
+    HIPCHK(c, grow(c, t.ends, n));
+    HIPCHK(c, hipMemcpyAsync(t.ends.p, ends, n * 8, hipMemcpyDefault, st));
+    d_ends = t.ends.p;
+  }
+  const uint32_t blocks = blocks_of(n);
+  const uint64_t cap = idset_table_cap(n);
+  HIPCHK(c, grow(c, t.slots, cap));
+  HIPCHK(c, grow(c, t.tot, kIdsetCounters));
+  HIPCHK(c, grow(c, w.flag, n));
+  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+
+  // ---- select ------------------------------------------------------------------
+  const uint64_t salt = idset_next_salt();
+  rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  PutArgs a{};
+  a.ids = d_ids;
+  a.ends = d_ends;
+  a.start = start;
+  a.n = n;
+  a.len = len;
+  a.blob = (const uint8_t*)d_blob;
+  a.slots = t.slots.p;
+  a.mask = cap - 1;
+  a.salt = salt;
+  a.st_ids = s->ids.p;
+  a.st_ends = s->ends.p;
+  a.st_slots = s->slots.p;
+  a.st_n = s->chunks;
+  a.st_mask = s->cap - 1;
+  a.st_salt = s->salt;
+  a.st_bytes = s->bytes;
+  a.flag = w.flag.p;
+  a.blk = w.blk.p;
+  a.tot = w.tot.p;
+  hipLaunchKernelGGL(store_select_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+  HIPCHK(c, hipGetLastError());
+  // ---- scan --------------------------------------------------------------------
+  hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
+  HIPCHK(c, hipGetLastError());
+  // ---- the one wait before any byte is copied ----------------------------------
+  u64 tot[kStoreCounters] = {};
+  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (tot[3]) return invalid(c, "chunk ends must be non-decreasing, start <= ends[0], ends[n-1] <= len");
+  const uint64_t stored = tot[0], stored_bytes = tot[1], present = tot[2];
+  if (totals) {
+    totals->total = n;
+    totals->stored = stored;
+    totals->stored_bytes = stored_bytes;
+    totals->present = present;
+    totals->repeats = n - stored - present;
+  }
+  if (stored > s->max_chunks - s->chunks || stored_bytes > s->arena_bytes - s->bytes) {
+    c->err = "the store is full: " + std::to_string(stored) + " chunks of " +
+             std::to_string(stored_bytes) + " bytes do not fit";
+    return DSX_E_CAPACITY;
+  }
+  if (!stored) return DSX_OK;
+  // ---- append, copy ------------------------------------------------------------
+  HIPCHK(c, grow(c, w.segs, 3 * stored));
+  a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
+  a.n_new = stored;
+  hipLaunchKernelGGL(store_append_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+  HIPCHK(c, hipGetLastError());
+  rc = assemble_launch(c, a.segs, stored, s->arena.p, s->bytes + stored_bytes, s->bytes,
+                       s->bytes + stored_bytes, false);
+  if (rc) return rc;
+  s->chunks += stored;  // (the launches are enqueued: the store has the chunks from here on)
+  s->bytes += stored_bytes;
+  HIPCHK(c, hipStreamSynchronize(st));
+  return DSX_OK;
+}
+
+// ids[idx ? idx[i] : i], i < m, looked up into d_offs / d_sizes (device, may be
+// null) with the missing count in w.tot[0]; enqueues only
+static int enqueue_lookup(dsx_ctx* c, const dsx_store* s, const uint8_t* d_ids, const uint32_t* d_idx,
+                          uint64_t m, uint64_t* d_offs, uint64_t* d_sizes) {
+  StoreScratch& w = c->store;
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), c->stream));
+  hipLaunchKernelGGL(store_lookup_kernel, dim3(blocks_of(m)), dim3(kStoreThreads), 0, c->stream, d_ids,
+                     d_idx, (u64)m, (const uint8_t*)s->ids.p, (const uint64_t*)s->ends.p,
+                     (const uint32_t*)s->slots.p, (u64)s->chunks, (u64)(s->cap - 1), (u64)s->salt,
+                     d_offs, d_sizes, w.tot.p);
+  HIPCHK(c, hipGetLastError());
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_locate(dsx_ctx_t* c, const dsx_store_t* s, const void* ids, uint64_t n,
+                                uint64_t* offs, uint64_t* sizes, uint64_t* n_missing,
+                                uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_out = DSX_OUT_DEVICE;
+  if (!c || !s) return DSX_E_INVAL;
+  if (n_missing) *n_missing = 0;
+  if ((flags & ~(f_ids | f_out)) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n && !ids) return invalid(c, "the IDs are missing");
+  if (n == 0) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint8_t* d_ids = nullptr;
+  int rc = stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  if (rc) return rc;
+  uint64_t* d_offs = offs;
+  if (offs && (!(flags & f_out) || !aligned(offs, 8))) {
+    HIPCHK(c, grow(c, w.offs, n));
+    d_offs = (uint64_t*)w.offs.p;
+  }
+  uint64_t* d_sizes = sizes;
+  if (sizes && (!(flags & f_out) || !aligned(sizes, 8))) {
+    HIPCHK(c, grow(c, w.sizes, n));
+    d_sizes = (uint64_t*)w.sizes.p;
+  }
+  rc = enqueue_lookup(c, s, d_ids, nullptr, n, d_offs, d_sizes);
+  if (rc) return rc;
+  if (offs && d_offs != offs) HIPCHK(c, hipMemcpyAsync(offs, d_offs, n * 8, hipMemcpyDefault, st));
+  if (sizes && d_sizes != sizes)
+    HIPCHK(c, hipMemcpyAsync(sizes, d_sizes, n * 8, hipMemcpyDefault, st));
+  u64 miss = 0;
+  HIPCHK(c, hipMemcpyAsync(&miss, w.tot.p, sizeof miss, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_missing) *n_missing = miss;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_entries(dsx_ctx_t* c, const dsx_store_t* s, uint64_t first, uint64_t n,
+                                 void* ids, uint64_t* ends, uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  if (!c || !s) return DSX_E_INVAL;
+  if ((flags & ~DSX_OUT_DEVICE) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (first > s->chunks || n > s->chunks - first)
+    return invalid(c, "first + n is beyond the store's entries");
+  if (n == 0) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  hipStream_t st = c->stream;
+  if (ids) HIPCHK(c, hipMemcpyAsync(ids, s->ids.p + 32 * first, n * 32, hipMemcpyDefault, st));
+  if (ends) HIPCHK(c, hipMemcpyAsync(ends, s->ends.p + first, n * 8, hipMemcpyDefault, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_resolve(dsx_ctx_t* c, const dsx_store_t* s, const void* ids, uint64_t n,
+                                 dsx_plan_seg_t* segs, uint64_t nsegs, uint64_t* n_missing,
+                                 uint64_t* n_wrong_size, uint32_t* first_bad, uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  if (!c || !s) return DSX_E_INVAL;
+  if (n_missing) *n_missing = 0;
+  if (n_wrong_size) *n_wrong_size = 0;
+  if (first_bad) *first_bad = 0xFFFFFFFFu;
+  if ((flags & ~DSX_IDS_DEVICE) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if ((n && !ids) || (nsegs && !segs)) return invalid(c, "the IDs or the segments are missing");
+  try {
+    std::vector<uint32_t> idx;    // the store segments' target positions ...
+    std::vector<uint64_t> where;  // ... and their numbers in segs[]
+    for (uint64_t i = 0; i < nsegs; ++i) {
+      const dsx_plan_seg_t& g = segs[i];
+      if ((uint64_t)g.first + g.count > n) {
+        c->err = "segment " + std::to_string(i) + ": first + count is beyond the target's chunks";
+        return DSX_E_INVAL;
+      }
+      if (g.source != DSX_SRC_STORE) continue;
+      if (g.first >= n) {
+        c->err = "segment " + std::to_string(i) + ": first names no target chunk";
+        return DSX_E_INVAL;
+      }
+      idx.push_back(g.first);
+      where.push_back(i);
+    }
+    const uint64_t m = idx.size();
+    if (m == 0) return DSX_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->err.clear();
+    StoreScratch& w = c->store;
+    hipStream_t st = c->stream;
+    const uint8_t* d_ids = nullptr;
+    int rc = stage_ids(c, ids, n, (flags & DSX_IDS_DEVICE) != 0, &d_ids);
+    if (rc) return rc;
+    HIPCHK(c, grow(c, w.idx, m));
+    HIPCHK(c, grow(c, w.offs, m));
+    HIPCHK(c, grow(c, w.sizes, m));
+    HIPCHK(c, hipMemcpyAsync(w.idx.p, idx.data(), m * 4, hipMemcpyHostToDevice, st));
+    rc = enqueue_lookup(c, s, d_ids, w.idx.p, m, (uint64_t*)w.offs.p, (uint64_t*)w.sizes.p);
+    if (rc) return rc;
+    std::vector<uint64_t> offs(m), sizes(m);
+    HIPCHK(c, hipMemcpyAsync(offs.data(), w.offs.p, m * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(sizes.data(), w.sizes.p, m * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    uint64_t miss = 0, wrong = 0;
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint64_t k = 0; k < m; ++k) {
+      const bool gone = offs[k] == UINT64_MAX;
+      const bool other = !gone && sizes[k] != segs[where[k]].bytes;
+      miss += gone;
+      wrong += other;
+      if (gone || other) bad = std::min(bad, idx[k]);
+    }
+    if (n_missing) *n_missing = miss;
+    if (n_wrong_size) *n_wrong_size = wrong;
+    if (first_bad) *first_bad = bad;
+    if (miss || wrong) return DSX_OK;
+    for (uint64_t k = 0; k < m; ++k) segs[where[k]].src_off = offs[k];
+    return DSX_OK;
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
+}
+
+extern "C" int dsx_store_verify(dsx_ctx_t* c, const dsx_store_t* s, int algo, uint32_t* bad,
+                                uint64_t cap, uint64_t* n_bad) {
+  DSX_FLUSH_BEHIND(c);
+  if (!c || !s) return DSX_E_INVAL;
+  if (n_bad) *n_bad = 0;
+  if (algo != DSX_DIGEST_SHA512_256 && algo != DSX_DIGEST_SHA256)
+    return invalid(c, "algo names no digest");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (cap && !bad) return invalid(c, "the list of bad entries is missing");
+  const uint64_t n = s->chunks;
+  if (n == 0) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  HIPCHK(c, grow(c, w.vids, n * 32));
+  HIPCHK(c, grow(c, w.flag, n));
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+  DigestArgs da{};
+  da.blob = s->arena.p;
+  da.len = s->bytes;
+  da.ends = s->ends.p;
+  da.first_start = 0;
+  da.n = n;
+  da.ids = w.vids.p;
+  int rc = launch_digest(c, da, n, algo);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  hipLaunchKernelGGL(store_compare_kernel, dim3(blocks_of(n)), dim3(kStoreThreads), 0, st,
+                     (const uint8_t*)w.vids.p, (const uint8_t*)s->ids.p, (u64)n, w.flag.p, w.tot.p);
+  HIPCHK(c, hipGetLastError());
+  u64 count = 0;
+  HIPCHK(c, hipMemcpyAsync(&count, w.tot.p, sizeof count, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_bad) *n_bad = count;
+  if (!count || !cap) return DSX_OK;
+  try {
+    std::vector<uint8_t> flag(n);  // (something is wrong: one byte per entry crosses)
+    HIPCHK(c, hipMemcpy(flag.data(), w.flag.p, n, hipMemcpyDeviceToHost));
+    uint64_t k = 0;
+    for (uint64_t e = 0; e < n && k < cap; ++e)
+      if (flag[e]) bad[k++] = (uint32_t)e;
+    return DSX_OK;
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
+}

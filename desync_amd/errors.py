@@ -20,3 +20,15 @@ class ChunkInvalid(Exception):
         if self.Err is not None:
             return f"invalid chunk {self.ID.hex()}: {self.Err}"
         return f"chunk id {self.ID.hex()} does not match its hash {(self.Sum or b'').hex()}"
+
+
+class ChunkMissing(KeyError):
+    """errors.go:5-17: the store does not hold the chunk.  A KeyError, so that
+    code written against MemoryStore still catches it."""
+
+    def __init__(self, ID: bytes):
+        self.ID = bytes(ID)
+        super().__init__(f"chunk {self.ID.hex()} missing from store")
+
+    def __str__(self):
+        return f"chunk {self.ID.hex()} missing from store"

@@ -23,7 +23,7 @@ import numpy as np
 
 from . import _lib, digest
 from ._lib import DSX_SRC_NULL, DSX_SRC_STORE, DsxError, lib
-from .errors import ChunkInvalid
+from .errors import ChunkInvalid, ChunkMissing
 from .index import ChunkArray, Index
 from .info import IDSet, _host_ids, _is_device
 from .make import chunk_ids
@@ -256,8 +256,8 @@ def NewSeedSequencer(index: Index, *seeds, null_seed=True, limit=0, ctx=None, de
 
 def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
     """dsx_assemble of a plan into the device tensor ``out``; ``store_bytes``
-    is the packed store buffer: host bytes (or a uint8 array), or a device
-    tensor."""
+    is the packed store buffer: host bytes (or a uint8 array), a device
+    tensor, or a ``(device pointer, length)`` pair (a DeviceStore's arena)."""
     sq = plan.sequencer
     ctx = ctx or sq.ctx
     ns = len(sq.seeds)
@@ -269,7 +269,9 @@ def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
         lens.append(ln)
     d_seeds = (ctypes.c_void_p * max(1, ns))(*ptrs)
     d_lens = (ctypes.c_uint64 * max(1, ns))(*lens)
-    if _is_device(store_bytes):
+    if isinstance(store_bytes, tuple):
+        sptr, slen, flags = int(store_bytes[0]), int(store_bytes[1]), flags | _lib.DSX_STORE_DEVICE
+    elif _is_device(store_bytes):
         sptr, slen, flags = store_bytes.data_ptr(), store_bytes.numel() * store_bytes.element_size(), \
             flags | _lib.DSX_STORE_DEVICE
     else:
@@ -292,7 +294,12 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
     match its index is skipped and the plan made again (InvalidSeedActionSkip,
     assemble.go:171-190); 3. the plan's ``store_chunks`` are fetched from
     ``store`` (``GetChunk(id) -> bytes``) and each length checked against the
-    index; 4. dsx_assemble; 5. dsx_chunk_ids of the result against the index's
+    index; 4. dsx_assemble (with a :class:`DeviceStore` of the same context
+    nothing is fetched: 3. is dsx_store_resolve, which points the plan's store
+    segments at the store's arena, and 4. reads the arena in place; a chunk the
+    store does not hold raises :class:`ChunkMissing`, a stored size that differs
+    from the index's ``ValueError("unexpected size for chunk <hex>")``,
+    assemble.go:75-77); 5. dsx_chunk_ids of the result against the index's
     IDs, the read-back check of assemble.go:208-229: a mismatch raises
     :class:`ChunkInvalid`.  An empty index gives an empty tensor
     (assemble.go:142-146).
@@ -327,19 +334,32 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
             break
         except SeedInvalid:
             sq.Rewind()  # the seed is marked: the next plan does without it
-    sizes = np.diff(sq.ends, prepend=np.uint64(0))
     raw = sq.ids.tobytes()
-    parts = []
-    for i in plan.store_chunks.tolist():
-        cid = raw[32 * i:32 * i + 32]
-        data = store.GetChunk(cid)
-        if len(data) != int(sizes[i]):
-            raise ChunkInvalid(cid, digest.Digest.Sum(data))
-        parts.append(bytes(data))
-    packed = b"".join(parts)
     length = int(sq.ends[-1])
     out = torch.empty(length, dtype=torch.uint8, device=dev)
-    assemble(plan, out, packed, ctx=ctx)
+    from .store import DeviceStore
+    if isinstance(store, DeviceStore) and store.ctx is ctx:
+        # the chunks are in HBM already: point the plan's store segments at the
+        # arena (dsx_store_resolve) and gather out of it in place
+        miss, wrong, bad = store.resolve(sq.ids, plan.segs)
+        if miss or wrong:
+            cid = raw[32 * bad:32 * bad + 32]
+            if not store.HasChunk(cid):
+                raise ChunkMissing(cid)
+            raise ValueError(f"unexpected size for chunk {cid.hex()}")  # assemble.go:75-77
+        with store._lock:
+            assemble(plan, out, store.arena(), ctx=ctx)
+    else:
+        sizes = np.diff(sq.ends, prepend=np.uint64(0))
+        parts = []
+        for i in plan.store_chunks.tolist():
+            cid = raw[32 * i:32 * i + 32]
+            data = store.GetChunk(cid)
+            if len(data) != int(sizes[i]):
+                raise ChunkInvalid(cid, digest.Digest.Sum(data))
+            parts.append(bytes(data))
+        packed = b"".join(parts)
+        assemble(plan, out, packed, ctx=ctx)
     got = chunk_ids(out.data_ptr(), length, sq.ends, 0, ctx=ctx)
     got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
     bad = np.flatnonzero(np.any(got != sq.ids, axis=1))

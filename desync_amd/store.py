@@ -1,0 +1,293 @@
+"""A chunk store in HBM: what desync puts between the write and the read side.
+
+Reference interface:
+    Store, WriteStore                     (store.go:21-33)
+    LocalStore with Uncompressed: true    (local.go, store.go:98-99)
+    LocalStore.Verify                     (local.go:103-161)
+    ChunkStorage.StoreChunk               (chunkstorage.go:44-67)
+    ChopFile                              (chop.go:14-81)
+    ChunkMissing                          (errors.go:5-17)
+
+:class:`DeviceStore` is an append-only, deduplicating arena of chunk bytes on
+the GPU, keyed by chunk ID (dsx_store_*).  It is filled from a
+blob resident in HBM by kernels (``put``: which chunks are new, where they go
+and the copy, without a host round trip per chunk) and read in place by
+dsx_assemble (:func:`desync_amd.AssembleBlob` with such a store fetches
+nothing through the host).  Its capacity is fixed when it is created.  Out of
+scope: removing chunks, growing, compression, persistence, a second context.
+"""
+from __future__ import annotations
+
+import ctypes
+import threading
+
+import numpy as np
+
+from . import _lib, digest
+from ._lib import DSX_ENDS_DEVICE, DsxError, lib
+from .errors import ChunkInvalid, ChunkMissing
+from .info import _ids_arg, _is_device
+from .make import _digest_code
+
+OFF_NONE = 0xFFFFFFFFFFFFFFFF  # locate's offset of an ID the store does not hold
+
+
+def _check(rc, ctx):
+    """check() with the context's detail for argument and capacity errors too."""
+    if rc < 0:
+        d = lib().dsx_last_error(ctx.h) if rc in (_lib.DSX_E_INVAL, _lib.DSX_E_CAPACITY) else None
+        if d:
+            raise DsxError(rc, d.decode())
+        _lib.check(rc, ctx.h)
+    return rc
+
+
+def _blob_arg(blob):
+    """-> (device pointer, length, object to keep alive) of a device tensor or
+    a ``(pointer, length)`` pair."""
+    if isinstance(blob, tuple):
+        return int(blob[0]), int(blob[1]), None
+    if _is_device(blob):
+        if not blob.is_contiguous():
+            raise ValueError("a blob must be contiguous")
+        return blob.data_ptr(), blob.numel() * blob.element_size(), blob
+    raise TypeError("a blob is a device tensor or a (device pointer, length) pair")
+
+
+class DeviceStore:
+    """A WriteStore in HBM (dsx_store_t) of up to ``max_chunks`` chunks and
+    ``arena_bytes`` bytes, belonging to one context.
+
+    ``HasChunk(id)``, ``StoreChunk(chunk)`` and ``GetChunk(id)`` are the
+    reference's interface, one chunk per call (StoreChunk uploads the host
+    bytes: the slow path, kept so that ChunkStorage and ChunkStream work with
+    it).  ``put`` / ``put_index`` store every chunk of a blob resident in HBM
+    in one call.  Every call holds the store's lock: ChunkStream's workers call
+    StoreChunk from several threads, and a context is not thread-safe."""
+
+    def __init__(self, arena_bytes, max_chunks, ctx=None, device=0):
+        self.ctx = ctx or _lib.default_context(device)
+        self.h = None
+        self._lock = threading.RLock()
+        h = ctypes.c_void_p()
+        _check(lib().dsx_store_create(self.ctx.h, int(arena_bytes), int(max_chunks), ctypes.byref(h)),
+               self.ctx)
+        self.h = h
+
+    # ---- the fill state ------------------------------------------------------------
+    def counts(self):
+        """dsx_store_counts_t as a dict: chunks, bytes, max_chunks, arena_bytes."""
+        with self._lock:
+            c = _lib.StoreCounts()
+            _lib.check(lib().dsx_store_count(self.h, ctypes.byref(c)))
+            return {k: getattr(c, k) for k, _ in _lib.StoreCounts._fields_}
+
+    def __len__(self):
+        return self.counts()["chunks"]
+
+    def arena(self):
+        """-> (device pointer of the arena, bytes in use): the store buffer of
+        dsx_assemble with DSX_STORE_DEVICE.  The pointer holds for the store's life."""
+        with self._lock:
+            p, used = ctypes.c_void_p(), ctypes.c_uint64()
+            _lib.check(lib().dsx_store_arena(self.h, ctypes.byref(p), ctypes.byref(used)))
+            return p.value or 0, used.value
+
+    def entries(self):
+        """-> (ids (chunks, 32) uint8, ends uint64): the stored IDs and their
+        cumulative arena ends, in arena order."""
+        with self._lock:
+            n = self.counts()["chunks"]
+            ids = np.empty((n, 32), dtype=np.uint8)
+            ends = np.empty(n, dtype=np.uint64)
+            if n:
+                _check(lib().dsx_store_entries(self.ctx.h, self.h, 0, n, ids.ctypes.data,
+                                               ends.ctypes.data, 0), self.ctx)
+            return ids, ends
+
+    # ---- the write side --------------------------------------------------------------
+    def put(self, blob, ids, ends, start=0, n=None):
+        """dsx_store_put: stores the chunks [start, ends[0]), [ends[0], ends[1]),
+        ... of ``blob`` (a device tensor or a ``(pointer, length)`` pair) under
+        ``ids`` (as for :class:`IDSet`: host or device).  ``ends`` is a host
+        array, a device tensor of uint64 or an integer device pointer.  The IDs
+        are trusted.  Returns the totals as a dict: total, stored,
+        stored_bytes, present, repeats.  A put that does not fit raises
+        DsxError (DSX_E_CAPACITY) with ``.totals`` what it would have stored,
+        and leaves the store unchanged."""
+        ptr, length, _keep_blob = _blob_arg(blob)
+        iptr, n, flags, _keep_ids = _ids_arg(ids, n)
+        if isinstance(ends, int):
+            eptr, _keep_ends = ends, None
+            flags |= DSX_ENDS_DEVICE
+        elif _is_device(ends):
+            if ends.numel() * ends.element_size() != 8 * n or not ends.is_contiguous():
+                raise ValueError("device ends must be n contiguous uint64")
+            eptr, _keep_ends = ends.data_ptr(), ends
+            flags |= DSX_ENDS_DEVICE
+        else:
+            _keep_ends = np.ascontiguousarray(ends, dtype=np.uint64)
+            if _keep_ends.size != n:
+                raise ValueError(f"{n} IDs but {_keep_ends.size} chunk ends")
+            eptr = _keep_ends.ctypes.data
+        tot = _lib.StorePutTotals()
+        with self._lock:
+            rc = lib().dsx_store_put(self.ctx.h, self.h, ctypes.c_void_p(ptr), length,
+                                     ctypes.c_void_p(iptr), ctypes.c_void_p(eptr), int(start), n,
+                                     ctypes.byref(tot), flags)
+            totals = {k: getattr(tot, k) for k, _ in _lib.StorePutTotals._fields_}
+            try:
+                _check(rc, self.ctx)
+            except DsxError as e:
+                e.totals = totals
+                raise
+        return totals
+
+    def put_index(self, blob, index):
+        """``put`` of the blob an :class:`Index` describes (its chunks start at 0)."""
+        from .extract import _index_arrays
+        ids, ends = _index_arrays(index)
+        return self.put(blob, ids, ends, 0)
+
+    def StoreChunk(self, chunk):
+        """WriteStore.StoreChunk: uploads the chunk's bytes and puts them as one
+        chunk (a chunk the store holds is skipped)."""
+        import torch
+        data = bytes(chunk.Data())
+        cid = bytes(chunk.ID())
+        with self._lock:
+            dev = f"cuda:{self.ctx.device}"
+            if data:
+                t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+                torch.cuda.synchronize(t.device)  # (torch's stream, not the context's)
+            else:
+                t = torch.empty(0, dtype=torch.uint8, device=dev)
+            self.put((t.data_ptr(), len(data)), np.frombuffer(cid, dtype=np.uint8).reshape(1, 32),
+                     np.array([len(data)], dtype=np.uint64))
+
+    # ---- the read side ---------------------------------------------------------------
+    def locate(self, ids, n=None):
+        """dsx_store_locate -> (offs, sizes, n_missing): the arena offset
+        (``OFF_NONE`` if the store does not hold the ID) and stored size (0 if
+        missing) per ID, as np.uint64."""
+        iptr, n, flags, _keep = _ids_arg(ids, n)
+        offs = np.empty(n, dtype=np.uint64)
+        sizes = np.empty(n, dtype=np.uint64)
+        miss = ctypes.c_uint64()
+        with self._lock:
+            _check(lib().dsx_store_locate(self.ctx.h, self.h, ctypes.c_void_p(iptr), n,
+                                          offs.ctypes.data, sizes.ctypes.data, ctypes.byref(miss),
+                                          flags), self.ctx)
+        return offs, sizes, miss.value
+
+    def HasChunk(self, cid) -> bool:
+        cid = bytes(cid)
+        miss = ctypes.c_uint64()
+        with self._lock:
+            _check(lib().dsx_store_locate(self.ctx.h, self.h, cid, 1, None, None, ctypes.byref(miss), 0),
+                   self.ctx)
+        return miss.value == 0
+
+    def GetChunk(self, cid) -> bytes:
+        """Store.GetChunk: the chunk's bytes, copied out of the arena;
+        :class:`ChunkMissing` if the store does not hold it."""
+        cid = bytes(cid)
+        with self._lock:
+            offs, sizes, miss = self.locate([cid])
+            if miss:
+                raise ChunkMissing(cid)
+            size = int(sizes[0])
+            out = np.empty(size, dtype=np.uint8)
+            if size:
+                base, _ = self.arena()
+                _lib.check(lib().dsx_copy(self.ctx.h, out.ctypes.data,
+                                          ctypes.c_void_p(base + int(offs[0])), size), self.ctx.h)
+            return out.tobytes()
+
+    def resolve(self, ids, segs, n=None):
+        """dsx_store_resolve on a plan's structured segment array (in place)
+        -> (n_missing, n_wrong_size, first_bad)."""
+        iptr, n, flags, _keep = _ids_arg(ids, n)
+        miss, wrong, bad = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        with self._lock:
+            _check(lib().dsx_store_resolve(self.ctx.h, self.h, ctypes.c_void_p(iptr), n,
+                                           ctypes.c_void_p(segs.ctypes.data), len(segs),
+                                           ctypes.byref(miss), ctypes.byref(wrong), ctypes.byref(bad),
+                                           flags), self.ctx)
+        return miss.value, wrong.value, bad.value
+
+    def Verify(self, algo=None):
+        """LocalStore.Verify (local.go:103-161): re-hashes every stored chunk in
+        the arena and returns the IDs of those that do not hash to their ID (an
+        empty list for a sound store).  ``algo`` defaults to the package-global
+        Digest.  Nothing is removed (no repair)."""
+        with self._lock:
+            bad = self.verify_entries(algo)
+            if not bad:
+                return []
+            ids, _ = self.entries()
+            return [ids[e].tobytes() for e in bad]
+
+    def verify_entries(self, algo=None):
+        """Verify() as ascending entry numbers."""
+        with self._lock:
+            n = self.counts()["chunks"]
+            bad = np.empty(max(1, n), dtype=np.uint32)
+            n_bad = ctypes.c_uint64()
+            _check(lib().dsx_store_verify(self.ctx.h, self.h, _digest_code(algo), bad.ctypes.data, n,
+                                          ctypes.byref(n_bad)), self.ctx)
+            return bad[:n_bad.value].tolist()
+
+    # ---- life ------------------------------------------------------------------------
+    def close(self):
+        with self._lock:
+            if self.h is not None:
+                if self.ctx.h:  # (a closed context has freed its stores)
+                    lib().dsx_store_destroy(self.ctx.h, self.h)
+                self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ChopBlob(index, blob, store, verify=True):
+    """ChopFile (chop.go:14-81) for a blob in HBM: stores every chunk of
+    ``index`` out of ``blob`` (a device tensor or a ``(pointer, length)``
+    pair) into ``store``, a :class:`DeviceStore`.
+
+    With ``verify`` every chunk is first re-hashed where it lies
+    (dsx_chunk_ids, NewChunkWithID's check, chunk.go:37-73) and compared with
+    the index; the first mismatch raises ``ChunkInvalid(id, sum)``.  Then comes
+    one ``put``.  Unlike ChopFile, whose workers may already have stored
+    earlier chunks when one turns out invalid, nothing is stored when a chunk
+    is invalid: the check of the whole blob comes before the put.  Returns the
+    put totals as a dict."""
+    from .extract import _index_arrays
+    from .make import chunk_ids
+    ids, ends = _index_arrays(index)
+    ptr, length, _keep = _blob_arg(blob)
+    if len(ends) and int(ends[-1]) > length:
+        raise EOFError("unexpected EOF")  # (io.ReadFull on a file shorter than its index)
+    if verify and len(ends):
+        with store._lock:
+            got = chunk_ids(ptr, length, ends, 0, ctx=store.ctx,
+                            algo=_digest_code(digest.Digest.Algorithm()))
+        got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
+        bad = np.flatnonzero(np.any(got != ids, axis=1))
+        if bad.size:
+            i = int(bad[0])
+            raise ChunkInvalid(ids[i].tobytes(), got[i].tobytes())
+    return store.put((ptr, length), ids, ends, 0)
+
+
+__all__ = ["DeviceStore", "ChopBlob", "OFF_NONE"]

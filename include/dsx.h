@@ -26,6 +26,9 @@
  *                           nullseed.go:45-74)
  *   dsx_assemble         <- AssembleFile's copy of the plan's segments,
  *                           assemble.go:93-309, for blobs resident in HBM
+ *   dsx_store_*          <- a LocalStore with Uncompressed: true (store.go:21-33,
+ *                           :98-99, local.go) and ChunkStorage.StoreChunk
+ *                           (chunkstorage.go:44-67), for chunks resident in HBM
  *
  * Conventions (cgo-safe): plain pointers and sizes only; no pointer passed in
  * is retained after a call returns; every function returns 0 or a negative
@@ -602,6 +605,109 @@ int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
                  const void *const *d_seeds, const uint64_t *seed_lens, uint32_t nseeds,
                  const void *store, uint64_t store_len, void *d_out, uint64_t out_len,
                  uint32_t flags);
+
+/* ---- a chunk store in HBM: what lies between the write and the read side -------
+ * The store desync puts between "which chunks are new" and "a plan plus the
+ * chunks no seed holds" (store.go:21-33, local.go, chunkstorage.go), for blobs
+ * that live in HBM: an append-only, deduplicating arena of chunk bytes keyed by
+ * chunk ID, filled from a resident blob by kernels and read in place by
+ * dsx_assemble.  The counterpart of a LocalStore with Uncompressed: true
+ * (store.go:98-99).  DESIGN.md 4.7 has the layout and the put's launches.
+ * A store belongs to the context that created it: it is used with that context
+ * only (a store of another context: DSX_E_INVAL with a dsx_last_error text),
+ * its memory counts in that context's device_bytes, and dsx_ctx_destroy frees
+ * the stores still alive.  Its capacity is fixed at creation and the arena is
+ * never reallocated, so its address is stable for the store's life.
+ * Out of scope: removing chunks, prune and compaction; growing a store;
+ * compression and encryption converters; persistence (dsx_store_entries plus
+ * the arena are enough for a caller to save and reload one); use from a second
+ * context or GPU. */
+typedef struct dsx_store dsx_store_t;
+
+/* A store of up to max_chunks chunks (<= 0xFFFFFFF0) and arena_bytes bytes. */
+int dsx_store_create(dsx_ctx_t *ctx, uint64_t arena_bytes, uint64_t max_chunks, dsx_store_t **out);
+int dsx_store_destroy(dsx_ctx_t *ctx, dsx_store_t *store);
+
+typedef struct dsx_store_counts {
+    uint64_t chunks, bytes, max_chunks, arena_bytes;
+} dsx_store_counts_t;
+int dsx_store_count(const dsx_store_t *store, dsx_store_counts_t *out);
+
+/* ChunkStorage.StoreChunk (chunkstorage.go:44-67) for every chunk of a resident
+ * blob. */
+typedef struct dsx_store_put_totals {
+    uint64_t total;        /* n */
+    uint64_t stored;       /* distinct chunks appended by this call */
+    uint64_t stored_bytes;
+    uint64_t present;      /* first occurrences in this call whose ID the store already held */
+    uint64_t repeats;      /* chunks repeating an earlier chunk of this call: total - stored - present */
+} dsx_store_put_totals_t;
+
+/* Stores the chunks [start, ends[0]), [ends[0], ends[1]), ... of d_blob[0..len)
+ * (device memory; d_blob[0] is position 0 of the offsets) under the IDs ids[]:
+ * ids/ends/start/n as in dsx_dedup without DSX_SIZES; flags DSX_IDS_DEVICE,
+ * DSX_ENDS_DEVICE, any other bit DSX_E_INVAL.  The IDs are trusted, as
+ * StoreChunk trusts chunk.ID(): dsx_chunk_ids before the put, or
+ * dsx_store_verify after it, is the check.  A chunk is appended exactly when it
+ * is the first occurrence of its ID in this call and the store does not hold
+ * that ID; new chunks are appended in the order of their first occurrence,
+ * tightly packed, entry e at [ends[e-1], ends[e]) of the arena; zero-length
+ * chunks take an entry of size 0.  The arena, the entry order and the totals
+ * (host memory, may be NULL) are exact and the same on every run.
+ * All or nothing: with chunks + stored > max_chunks or bytes + stored_bytes >
+ * arena_bytes the call returns DSX_E_CAPACITY, the totals say what it would
+ * have stored, and the store is unchanged.  Checked before any byte is copied,
+ * each DSX_E_INVAL with a dsx_last_error text and the store unchanged: the
+ * chunk list (start <= ends[0], non-decreasing, ends[n-1] <= len; host ends on
+ * the host, device ends by the selecting kernel) and the blob not overlapping
+ * the arena.  No kernel reads outside d_blob[0, len) or writes outside the
+ * arena.  n == 0: zero totals, DSX_OK.  n > 0xFFFFFFF0: DSX_E_INVAL.
+ * Synchronous on the ctx stream: one host wait between selecting and copying,
+ * one at the end. */
+int dsx_store_put(dsx_ctx_t *ctx, dsx_store_t *store, const void *d_blob, uint64_t len,
+                  const void *ids, const uint64_t *ends, uint64_t start, uint64_t n,
+                  dsx_store_put_totals_t *totals, uint32_t flags);
+
+/* HasChunk / GetChunk's lookup (store.go:22-23; ChunkMissing) for n IDs:
+ * offs[i] = the arena offset of the chunk with ids[i] or UINT64_MAX if the
+ * store does not hold it, sizes[i] = its stored size or 0, *n_missing the
+ * number of IDs not held; each output may be NULL.  flags: DSX_IDS_DEVICE,
+ * DSX_OUT_DEVICE (offs and sizes are device memory). */
+int dsx_store_locate(dsx_ctx_t *ctx, const dsx_store_t *store, const void *ids, uint64_t n,
+                     uint64_t *offs, uint64_t *sizes, uint64_t *n_missing, uint32_t flags);
+
+/* The arena for dsx_assemble: store = *d_arena, store_len = *used, with
+ * DSX_STORE_DEVICE. */
+int dsx_store_arena(const dsx_store_t *store, const void **d_arena, uint64_t *used);
+
+/* The IDs (n * 32 bytes) and cumulative arena ends of entries [first, first + n),
+ * in arena order; either may be NULL.  Host memory, or device with
+ * DSX_OUT_DEVICE.  first + n beyond the entries: DSX_E_INVAL. */
+int dsx_store_entries(dsx_ctx_t *ctx, const dsx_store_t *store, uint64_t first, uint64_t n,
+                      void *ids, uint64_t *ends, uint32_t flags);
+
+/* Points a plan's DSX_SRC_STORE segments at the arena.  ids/n are the target's
+ * IDs (host memory, or DSX_IDS_DEVICE), segs[nsegs] host memory.  For every
+ * segment with source == DSX_SRC_STORE the store is asked for ids[first]: a
+ * chunk it does not hold counts in *n_missing, a stored size different from
+ * the segment's bytes in *n_wrong_size ("unexpected size for chunk",
+ * assemble.go:75-77); *first_bad is the lowest target position with either
+ * problem, else 0xFFFFFFFF.  With both counts zero each such segment's src_off
+ * becomes the chunk's arena offset; otherwise segs is left untouched.  DSX_OK
+ * in both cases (the counts are the answer).  Other segments are never
+ * touched.  first + count > n in any segment: DSX_E_INVAL. */
+int dsx_store_resolve(dsx_ctx_t *ctx, const dsx_store_t *store, const void *ids, uint64_t n,
+                      dsx_plan_seg_t *segs, uint64_t nsegs, uint64_t *n_missing,
+                      uint64_t *n_wrong_size, uint32_t *first_bad, uint32_t flags);
+
+/* LocalStore.Verify (local.go:103-161): re-hashes every stored chunk where it
+ * lies (algo: DSX_DIGEST_*, the store does not know which digest made its IDs)
+ * and compares the result with the stored IDs on the device.  bad[] (host
+ * memory) receives the ascending entry numbers of the mismatches, min(cap,
+ * *n_bad) of them, *n_bad the full count.  The computed IDs stay in the
+ * context's scratch (device_bytes). */
+int dsx_store_verify(dsx_ctx_t *ctx, const dsx_store_t *store, int algo, uint32_t *bad,
+                     uint64_t cap, uint64_t *n_bad);
 
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
