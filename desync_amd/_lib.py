@@ -199,7 +199,7 @@ def _share_torch_hip_runtime():
 
 # The DSX_* settings the product library reads (INTEGRATION.md,
 # "Environment"; tests/test_abi.py checks the library's strings against it).
-PRODUCT_ENV = ("DSX_TAIL_SPLIT", "DSX_LANE_TARGET", "DSX_SEG_FLOOR", "DSX_SCAN_NT",
+PRODUCT_ENV = ("DSX_TAIL_SPLIT", "DSX_LANE_TARGET", "DSX_SEG_FLOOR", "DSX_SCAN_NT", "DSX_SCAN_ROTF",
                "DSX_DIGEST_PC", "DSX_DIGEST_LPT", "DSX_INDEX_WINDOW", "DSX_INDEX_SLOT",
                "DSX_INDEX_READERS", "DSX_INDEX_HOST_TAIL", "DSX_HOST_THREADS")
 # Settings only libdsx_diag.so reads (scan ablations, other geometries,

@@ -176,6 +176,7 @@ extern "C" int dsx_ctx_create(int device, dsx_ctx_t** out) {
     c->lane_target = (uint32_t)std::max(384, std::min((int)kLineLaneMax, atoi(v)));
   if (const char* v = getenv("DSX_SEG_FLOOR")) c->seg_floor = (uint64_t)std::max(0L, atol(v));
   if (const char* v = getenv("DSX_SCAN_NT")) c->scan_nt = atoi(v) & 3;
+  if (const char* v = getenv("DSX_SCAN_ROTF")) c->scan_rotf = atoi(v) != 0;
   if (const char* v = getenv("DSX_DIGEST_PC")) c->digest_pc = atoi(v);
   if (const char* v = getenv("DSX_DIGEST_LPT")) c->digest_lpt = atoi(v) != 0;
   if (const char* v = getenv("DSX_INDEX_WINDOW")) c->index_window = (uint64_t)std::max(1L << 16, atol(v));
@@ -850,6 +851,12 @@ int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_
     if (line) {
       DSX_ABLATEL(scanl_kernel, 8, 8, 1)
       DSX_TRACE_VARIANTS(8, 8, 1)
+      if (c->scan_rotf && mode == 2) {  // the rotating frame (MODE 2 only)
+        if (sa.lane_bytes2)
+          hipLaunchKernelGGL((scanl_kernel<2, 0, 8, 8, 1, false, true, true>), g, b, 0, ss, sa);
+        else
+          hipLaunchKernelGGL((scanl_kernel<2, 0, 8, 8, 1, false, false, true>), g, b, 0, ss, sa);
+      } else
       if (sa.lane_bytes2) DSX_LAUNCHL(8, 8, 1, false, true);  // two region sizes
       else DSX_LAUNCHL(8, 8, 1, false, false);
     } else {

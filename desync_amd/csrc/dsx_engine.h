@@ -23,8 +23,8 @@ template <class H>
 __global__ void digest_pc_kernel(DigestArgs a);
 template <int MODE, int VARIANT, int BR, int NBUF, int W, int SUB, bool PF>
 __global__ void scan_kernel(ScanArgs a);
-template <int MODE, int VARIANT, int W, int SUB, int D, bool FUSE, bool TWO>
-__global__ void scanl_kernel(ScanArgs a);  // TWO: two region sizes (ScanArgs.lane_bytes2)
+template <int MODE, int VARIANT, int W, int SUB, int D, bool FUSE, bool TWO, bool ROTF = false>
+__global__ void scanl_kernel(ScanArgs a);  // TWO: two region sizes (ScanArgs.lane_bytes2); ROTF: dsx_rotframe.h
 __global__ void stitch_task_kernel(TaskArgs b);
 template <int NT>
 __global__ void walk_kernel(StitchArgs a);
@@ -141,6 +141,7 @@ struct dsx_ctx {
   int walk_nt = 576;                  // DSX_WALK_NT: 576 = one wave per chain at 8 segments per workgroup (256: 4 waves)
   bool scan_trace = false;            // DSX_SCAN_TRACE: per-wave timestamps of the last scan
   bool wave_major = true;             // DSX_WAVE_MAJOR: scanl's first regions wave-major
+  bool scan_rotf = true;              // DSX_SCAN_ROTF=0: the MODE 2 line scan without the rotating frame (dsx_rotframe.h)
   int scan_nt = 1;                    // DSX_SCAN_NT: line DMA cache policy (0 none, 1 nt: default, 2 sc1, 3 sc0 sc1 nt)
   bool finish = true;                 // DSX_FINISH=0: fixup_fast_kernel + gather_kernel instead of finish_kernel
   bool fixup_fast = true;             // DSX_FIXUP_FAST=0: fixup_kernel for every piece

@@ -20,7 +20,9 @@
 //     (byte v, slot s at v*256 + s*8 = {T[v], rotl16(T[v])}) so each lookup is
 //     ONE v_perm_b32 (address = byte<<8 | slot) + ONE conflict-free
 //     ds_read_b64; the outgoing byte's rotated term comes from a 48-entry
-//     register ring;
+//     register ring (MODE 2 by default keeps the hash in a rotating frame
+//     instead, dsx_rotframe.h: 64 slots of 4 B, slot s = rotl^(s & 31) T[v],
+//     ONE v_perm_b32 + ONE ds_read_b32 per byte and no rotated copy);
 //   * the boundary test is ONE cvt + ONE fma + ONE 24-bit mad + ONE compare
 //     (magic-number rounding, exact for 1024 < d < 2^22), a wave ballot per
 //     byte, and one scalar branch per 16 bytes for the rare hits;
@@ -33,6 +35,7 @@
 #include <utility>
 #include "dsx_chain.h"
 #include "dsx_common.h"
+#include "dsx_rotframe.h"
 #include "dsx_stitch.h"
 #if DSX_DIAG  // the stitch behind the scan (DSX_FUSE): libdsx_diag.so only
 #include "dsx_tasks.h"
@@ -300,6 +303,12 @@ __device__ __forceinline__ void lookups_landed(uint64_t (&L)[SUB]) {
     static_assert(SUB == 4, "SUB is 4 or 8");
     asm volatile("" : "+v"(L[0]), "+v"(L[1]), "+v"(L[2]), "+v"(L[3]));
   }
+}
+
+// (the same for 8 lookups that landed in single registers: scanl_kernel<ROTF>)
+__device__ __forceinline__ void lookups_landed_u32(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d,
+                                                uint32_t& e, uint32_t& f, uint32_t& g, uint32_t& h) {
+  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
 }
 
 // Hash bytes [0, NB) of w (byte i is byte i&3 of w[i>>2]); byte i uses ring
@@ -713,8 +722,19 @@ DSX_SCAN_INST_ALL(2, 1, 16, 4, false)
 // the grid has beyond the regions at once, the others once the regions run
 // out ("stitch behind the scan").
 // ---------------------------------------------------------------------------
-template <int MODE, int VARIANT, int W, int SUB, int D, bool FUSE, bool TWO>
+//
+// ROTF (the default for MODE 2, DSX_SCAN_ROTF): the hash is kept in the
+// rotating frame of dsx_rotframe.h.  The table holds 64 slots of 4 B per byte value (slot k =
+// rotl^(k & 31) T), a lookup is one v_perm_b32 + one conflict-free
+// ds_read_b32 into a 64-register ring that serves as incoming term at once
+// and as outgoing term 48 bytes later, and one v_alignbit_b32 per byte turns
+// the frame back in front of the unchanged boundary test.
+// ---------------------------------------------------------------------------
+template <int MODE, int VARIANT, int W, int SUB, int D, bool FUSE, bool TWO, bool ROTF = false>
 __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
+  static_assert(!ROTF || (MODE == 2 && VARIANT == 0 && D == 1 && !FUSE),
+                "the rotating frame is built for the exact MODE 2 kernel at D = 1");
+  static_assert(!ROTF || rotframe::kTableBytes == kTableBytes, "table size");
   constexpr int NC = kLine / 16;             // 16-B chunks per lane row
   constexpr int NI = kWave * kLine / 1024;   // DMA wave instructions per batch
   constexpr int STG = kWave * kLine;         // staging bytes per wave
@@ -816,6 +836,16 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
   uint32_t qlim_v = tcv.qmax + tcv.qbias, rot_v = tcv.rot;
   asm volatile("" : "+v"(qlim_v));
   asm volatile("" : "+v"(rot_v));
+  // ROTF: the 32 phase registers {s, slot * 4} of this lane, one per stream
+  // position mod 32 (opaque, so they are kept and not recomputed per use)
+  uint32_t ph[ROTF ? rotframe::kPhases : 1];
+  if constexpr (ROTF) {
+#pragma unroll
+    for (int f = 0; f < rotframe::kPhases; ++f) {
+      ph[f] = rotframe::phase_reg(lane, (uint32_t)f);
+      asm volatile("" : "+v"(ph[f]));
+    }
+  }
 
   // Region r's descriptor starts at its warm-up line (grid-relative
   // r*RB - 128), shifted by shift0 for region 0 so it never precedes the
@@ -944,7 +974,20 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  {
+  if constexpr (ROTF) {
+    // slot k of byte value v = rotl^(k & 31) T[v] at v*256 + k*4: dword e of
+    // the table is {v = e >> 6, slot = e & 63}, so a wave writes one value's
+    // 64 slots, 256 consecutive bytes, from a broadcast read of T[v]
+    static_assert(NT % 64 == 0, "table fill shape");
+    const uint32_t slot = threadIdx.x & 63u;
+    const uint32_t rr = 32u - rotframe::slot_rot(slot);  // rotl s == rotr (32 - s); bits [4:0] used
+#pragma unroll 4
+    for (uint32_t e = threadIdx.x; e < 256u * rotframe::kSlots; e += NT) {
+      const uint32_t tv = s_tab[e >> 6];
+      *reinterpret_cast<uint32_t*>(lds + rotframe::table_offset(e >> 6, slot)) =
+          __builtin_amdgcn_alignbit(tv, tv, rr);
+    }
+  } else {
     constexpr int TPV = NT / 256;  // threads per byte value
     const uint32_t v = threadIdx.x & 255u;
     const uint32_t tv = s_tab[v];
@@ -1041,10 +1084,14 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
     uint32_t* myslots = a.lane_slot + gl * a.lane_slots;
     // MODE 2 keeps ~h: rotl1(~x) == ~rotl1(x), so ~h follows the same
     // recurrence from ~0, and t + 1 = (h+1)*inv = (~h)*ninv (make_tc)
+    // (ROTF: h is g, the hash in the rotating frame; ~0 is the same in every
+    // frame.  Its ring is the last 64 lookups, each written before it is read)
     uint32_t h = MODE == 2 ? ~0u : 0u;
-    uint32_t ring[48];
+    uint32_t ring[ROTF ? rotframe::kRing : 48];
+    if constexpr (!ROTF) {
 #pragma unroll
-    for (int k = 0; k < 48; ++k) ring[k] = 0;
+      for (int k = 0; k < 48; ++k) ring[k] = 0;
+    }
     uint32_t w[NC * 4];
 
     // wait for batch b, copy this lane's row to registers, issue batch b+1
@@ -1104,8 +1151,37 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
     };
     fetch(0u);
     // warm-up: the last 48 bytes before the segment fill the window (no test)
-    hash_span<kRound, 0, false, MODE, VARIANT, SUB>(w + 20, h, ring, lds, slot8, tcv, lane, 0u,
-                                                    cnt, ereg, myslots, 0u);
+    if constexpr (ROTF) {
+      // positions -48 .. -1: nothing leaves the window yet (g ^= U), and the
+      // lookups stay in the ring as the outgoing terms of positions 0 .. 47
+      auto warm_issue = [&](auto jc) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const int k = j * 8 + q;  // byte of the span w[20 ..]
+          const int i = k - rotframe::kWindow;
+          ring[rotframe::ring_in(i)] = *reinterpret_cast<const uint32_t*>(
+              lds + __builtin_amdgcn_perm(w[20 + (k >> 2)], ph[rotframe::phase_of(i)],
+                                          rotframe::lookup_sel(k & 3)));
+        }
+      };
+      warm_issue(std::integral_constant<int, 0>{});
+      static_for<6>([&](auto jc) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (j + 1 < 6) warm_issue(std::integral_constant<int, j + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int r0 = rotframe::ring_in(j * 8 - rotframe::kWindow);
+        lookups_landed_u32(ring[r0], ring[r0 + 1], ring[r0 + 2], ring[r0 + 3], ring[r0 + 4],
+                        ring[r0 + 5], ring[r0 + 6], ring[r0 + 7]);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) h ^= ring[r0 + q];
+      });
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
+      hash_span<kRound, 0, false, MODE, VARIANT, SUB>(w + 20, h, ring, lds, slot8, tcv, lane, 0u,
+                                                      cnt, ereg, myslots, 0u);
+    }
     // Steady state: trips of 3 lines (384 B = 8 windows, so ring slots are
     // static) as 48 subgroups of 8 bytes.  The table lookups run one subgroup
     // ahead, ACROSS line boundaries: once the last subgroup of a line has
@@ -1116,13 +1192,17 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
     static_assert(SUB == 8, "trip pipeline is written for 8-byte subgroups");
     static_assert(D >= 1 && D <= 15 && 48 % (D + 1) == 0, "lookup distance");
     constexpr int NL = D + 1;
-    uint64_t L[NL][8];
+    uint64_t L[NL][8];  // (unused with ROTF: the lookups land in the ring)
     auto issue_sub = [&](auto gc) __attribute__((always_inline)) {
       constexpr int g = decltype(gc)::value;
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const int k = (g % 16) * 8 + q;  // byte within the line
-        if constexpr (VARIANT == 7 || VARIANT == 10)
+        if constexpr (ROTF)
+          ring[rotframe::ring_in(g * 8 + q)] = *reinterpret_cast<const uint32_t*>(
+              lds + __builtin_amdgcn_perm(w[k >> 2], ph[rotframe::phase_of(g * 8 + q)],
+                                          rotframe::lookup_sel(k & 3)));
+        else if constexpr (VARIANT == 7 || VARIANT == 10)
           L[g % NL][q] = *reinterpret_cast<const uint32_t*>(lds + lookup_addr(w[k >> 2], slot8, k & 3));
         else
           L[g % NL][q] = *reinterpret_cast<const uint64_t*>(lds + lookup_addr(w[k >> 2], slot8, k & 3));
@@ -1135,7 +1215,13 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
         asm volatile("" ::"v"(h));
         return;
       }
-      lookups_landed<8>(L[g % NL]);
+      if constexpr (ROTF) {
+        constexpr int r0 = rotframe::ring_in(g * 8);
+        lookups_landed_u32(ring[r0], ring[r0 + 1], ring[r0 + 2], ring[r0 + 3], ring[r0 + 4],
+                        ring[r0 + 5], ring[r0 + 6], ring[r0 + 7]);
+      } else {
+        lookups_landed<8>(L[g % NL]);
+      }
       // (energy ablations, wrong results: 8 = no multiply (t = h), 9 = the 8 t
       // values OR-ed with full-rate v_bitop3 instead of the v_min3 tree, 10 =
       // 4-byte lookups, the ring takes T itself)
@@ -1146,6 +1232,15 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
       uint32_t t[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
+        if constexpr (ROTF) {
+          // g ^= U_i ^ U_{i-48} (one xor3), x = rotr^s(g) (one v_alignbit,
+          // amount in the phase register), t + 1 = x * ninv
+          constexpr int i0 = g * 8;
+          h = __builtin_amdgcn_bitop3_b32(h, ring[rotframe::ring_in(i0 + q)],
+                                          ring[rotframe::ring_out(i0 + q)], 0x96);
+          t[q] = __builtin_amdgcn_alignbit(h, h, ph[rotframe::phase_of(i0 + q)]) * tcv.ninv;
+          continue;
+        }
         const int rk = (g * 8 + q) % 48;
         const uint32_t outv =
             VARIANT == 7 ? __builtin_amdgcn_alignbit(ring[rk], ring[rk], 16) : ring[rk];
@@ -1461,6 +1556,10 @@ template __global__ void scanl_kernel<2, 8, 8, 8, 1, false, false>(ScanArgs);
 template __global__ void scanl_kernel<2, 9, 8, 8, 1, false, false>(ScanArgs);
 template __global__ void scanl_kernel<2, 10, 8, 8, 1, false, false>(ScanArgs);
 #endif
+// the rotating frame (the default for MODE 2; DSX_SCAN_ROTF=0 selects the kernel
+// without it), one and two region sizes
+template __global__ void scanl_kernel<2, 0, 8, 8, 1, false, false, true>(ScanArgs);
+template __global__ void scanl_kernel<2, 0, 8, 8, 1, false, true, true>(ScanArgs);
 DSX_SCANL_INST(8, 8, 1)  // D = 2 needs 16 more VGPRs than the 256 of two waves per SIMD
 
 // Exhaustive/ranged check of the GPU boundary predicate against h % d == d-1
