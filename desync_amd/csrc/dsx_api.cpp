@@ -1609,9 +1609,8 @@ static int shard_run(dsx_ctx* c, uint64_t entry, uint32_t rec_flags, bool rewalk
                            is_last && i + 1 == sh.nkept, ++c->piece_seq, false);
       }
       if (rc) return rc;
-      hipLaunchKernelGGL(seam_cands_kernel, dim3(1), dim3(64), 0, c->stream, sh.kept[0].pc,
-                         sh.start, wend0, c->d_seam.p);
-      HIPCHK(c, hipGetLastError());
+      // (no seam_cands_kernel: a re-walked record carries no window,
+      // seam_finalize_kernel empties its lists)
     } else {
       sh.nkept = 0;  // (the buffers are reused)
       cc.keep = dense ? nullptr : &sh.kept;

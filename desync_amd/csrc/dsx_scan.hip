@@ -58,6 +58,27 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 __constant__ uint32_t kT[256] = DSX_BUZHASH_TABLE_INIT;
 
+// scan_kernel's piece end: the candidates among the positions lane_rel + o,
+// o in [t_lo, t_hi] (at most three, bit o - t_lo), hashed from byte loads by
+// the plain form of chunker.go:225-228 and tested as h % d == d - 1.  Window
+// bytes before the readable halo are zeros, as for the DMA.
+__device__ __noinline__ uint32_t tail_hits(const uint8_t* base, uint64_t halo, uint32_t d,
+                                           uint64_t lane_rel, uint32_t t_lo, uint32_t t_hi) {
+  uint32_t mask = 0u;
+  for (uint32_t o = t_lo; o <= t_hi; ++o) {
+    const int64_t w0 = (int64_t)(lane_rel + o) - kRound;  // piece-relative window start
+    uint32_t h = 0u;
+    for (int i = 0; i < kRound; ++i) {
+      const int64_t idx = w0 + i;
+      const uint32_t v = kT[idx >= -(int64_t)halo ? base[idx] : 0u];
+      const uint32_t r = (uint32_t)(kRound - 1 - i) & 31u;
+      h ^= (v << r) | (v >> ((32u - r) & 31u));
+    }
+    if (h % d == d - 1u) mask |= 1u << (o - t_lo);
+  }
+  return mask;
+}
+
 // One 1 KiB LDS-DMA wave instruction (buffer_load_dwordx4 ... lds): lane j's
 // 16 bytes from rsrc+voff land at LDS byte lds_addr + 16*j.  Inline asm so
 // hipcc does not treat later ds_reads as aliasing a pending DMA (it would
@@ -500,6 +521,12 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scan_kernel(ScanArgs a) {
     const uint32_t H = (rbase + a.halo >= (uint64_t)kRound) ? (uint32_t)kRound
                                                              : (uint32_t)(rbase + a.halo);
     const uint8_t* rptr = a.base + rbase - H;
+    // (a dword that straddles the end of the range reads as zeros whole, and
+    // every load here is a multiple of 4 bytes from base: the piece's last
+    // len % 4 bytes come in as zeros.  scanl_kernel widens its range to the
+    // aligned word; base is unaligned here and that word may reach into a
+    // page the caller does not own, so the range stays exact and the region
+    // end below hashes the last len % 4 positions again from byte loads)
     const uint64_t nrec64 = a.len - rbase + H;
     const uint32_t nrec = nrec64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)nrec64;
     const uint64_t rp = (uint64_t)(uintptr_t)rptr;
@@ -624,12 +651,25 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scan_kernel(ScanArgs a) {
     const uint32_t o_min = lane_abs >= a.min_pos ? 0u : (uint32_t)(a.min_pos - lane_abs);
     const uint32_t n = cnt < a.lane_slots + kHitRegs ? cnt : a.lane_slots + kHitRegs;
     const bool spilled = __ballot(cnt > (uint32_t)kHitRegs) != 0;  // rare: global reads
+    // The piece's last len % 4 bytes came in as zeros (desc_of), so the
+    // hashes at its last len % 4 positions are wrong: the lane (two, if they
+    // straddle a lane border) that holds them drops its hits at the offsets
+    // [t_lo, t_hi] and takes them from tail_hits instead.  (No lane: t_hi = 0.)
+    uint32_t t_lo = 1u, t_hi = 0u, tmask = 0u;
+    if (const uint32_t k0 = (uint32_t)(a.len & 3u); k0 != 0u && seg_valid != 0u) {
+      const uint64_t first = a.len - k0 + 1u;  // piece-relative
+      if (lane_rel + seg_valid >= first) {
+        t_hi = seg_valid;
+        t_lo = first > lane_rel + 1u ? (uint32_t)(first - lane_rel) : 1u;
+        tmask = tail_hits(a.base, a.halo, a.tc.d, lane_rel, t_lo, t_hi);
+      }
+    }
     auto for_each_hit = [&](auto&& f) {
       auto expand = [&](uint32_t e) {
         const uint32_t base = e & 0xFFFFu;
         for (uint32_t bits = e >> 16; bits; bits &= bits - 1u) {
           const uint32_t o = base + (uint32_t)__builtin_ctz(bits) + 1u;  // offset in lane seg
-          if (o >= o_min && o <= seg_valid) f(o);
+          if (o >= o_min && o <= seg_valid && (o < t_lo || o > t_hi)) f(o);
         }
       };
 #pragma unroll
@@ -637,6 +677,10 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scan_kernel(ScanArgs a) {
         if ((uint32_t)q < n) expand(ereg[q]);
       if (spilled)
         for (uint32_t i = kHitRegs; i < n; ++i) expand(myslots[i - kHitRegs]);
+      for (uint32_t m = tmask; m; m &= m - 1u) {  // (the lane's highest offsets: still sorted)
+        const uint32_t o = t_lo + (uint32_t)__builtin_ctz(m);
+        if (o >= o_min) f(o);
+      }
     };
     uint32_t keep = 0;
     for_each_hit([&](uint32_t) { ++keep; });
@@ -854,7 +898,14 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
     sh = region == 0 ? a.shift0 : 0u;
     const int64_t rel = (int64_t)region_base(region) - (int64_t)a.delta - kLine + (int64_t)sh;
     const uint64_t rp = (uint64_t)(uintptr_t)(a.base + rel);
-    const uint64_t nrec64 = (uint64_t)((int64_t)a.len - rel);
+    // The range ends with the aligned 4-byte word that holds the piece's last
+    // byte (rp is a multiple of 16): a dword that straddles the end of the
+    // range reads as zeros whole, which made the hashes at the last one to
+    // three positions of a piece wrong when it ended off the 4-byte grid (a
+    // shard that ends inside the blob: a candidate there missed, or a
+    // spurious one).  The bytes past len lie in the same word, so in the same
+    // page, and only feed positions past len, which are dropped below.
+    const uint64_t nrec64 = ((uint64_t)((int64_t)a.len - rel) + 3ull) & ~3ull;
     const uint32_t nrec = nrec64 > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)nrec64;
     rsrc.x = __builtin_amdgcn_readfirstlane((uint32_t)rp);
     rsrc.y = __builtin_amdgcn_readfirstlane((uint32_t)(rp >> 32) & 0xFFFFu);

@@ -1068,6 +1068,14 @@ __global__ void seam_finalize_kernel(dsx_seam_t* seam, const uint64_t* cuts, con
   }
   uint32_t ncand = 0;
   while (ncand < seam->ncands && seam->cands[ncand] <= wend) ++ncand;
+  if (flags & DSX_SEAM_REWALKED) {
+    // a re-walked chain is true from `entry` on: seam_resolve_kernel reads
+    // its entry and exit cut alone, and the record carries no window (its
+    // cuts would not be a speculative chain's), as oracle/seam.py's rewalk
+    wend = shard_start;
+    ncand = nc = 0;
+    seam->first_cand_beyond = ~0ull;
+  }
   seam->shard_start = shard_start;
   seam->shard_len = shard_len;
   seam->total = total;

@@ -262,13 +262,15 @@ int dsx_host_sha512_256(const uint8_t *const *ptrs, const uint64_t *lens, uint64
 #define DSX_SEAM_MAX_CUTS 1024
 #define DSX_SEAM_DEVICE 8u      /* flag: seam records are device memory */
 #define DSX_SEAM_LAST 1u        /* seam flags: the shard ends the blob */
-#define DSX_SEAM_REWALKED 2u    /* seam flags: chain re-walked from the true entry `entry` */
+#define DSX_SEAM_REWALKED 2u    /* seam flags: chain re-walked from the true entry `entry`; the record
+                                   carries no window (window_end == shard_start, ncands == ncuts == 0) */
 #define DSX_SEAM_ERROR 4u       /* seam flags: the owner failed; every rank's resolve returns DSX_E_PEER */
 #define DSX_SEAM_REDO 16u       /* seam flags: an asynchronous dsx_shard_local hit a stitch error; the
                                    owner redoes its shard synchronously (dsx_shard_collect) */
 typedef struct dsx_seam {
     uint64_t shard_start, shard_len, total;
-    uint64_t first_cand_beyond;   /* first candidate > window end, or UINT64_MAX */
+    uint64_t first_cand_beyond;   /* the first window candidate that did not fit cands[] (the 1025th
+                                     of the shard's first 32*max bytes), or UINT64_MAX */
     uint64_t exit_cut;            /* the shard chain's last cut <= shard end */
     uint64_t window_end;          /* candidates/cuts below cover (shard_start, window_end] */
     uint64_t entry;               /* DSX_SEAM_REWALKED: the entry cut the chain started from */
@@ -712,7 +714,7 @@ int dsx_store_verify(dsx_ctx_t *ctx, const dsx_store_t *store, int algo, uint32_
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
     uint64_t chunks;            /* ChunksAccepted */
-    uint64_t candidates;        /* boundary candidates found by the scan */
+    uint64_t candidates;        /* reserved, always 0 (the scan's candidate counts stay on the device) */
     uint64_t pieces;            /* scan pieces processed */
     uint64_t repaired_segments; /* segments that needed the sequential repair */
     uint64_t dense_fallbacks;   /* pieces processed on the dense-candidate path */

@@ -51,17 +51,29 @@ SEAM_LAST = 1
 SEAM_REWALKED = 2
 
 
-def shard_local(full, start, length, total, mn, av, mx, max_cands=1024, max_cuts=1024):
+def shard_local(full, start, length, total, mn, av, mx, max_cands=1024, max_cuts=1024,
+                cands=None):
     """Seam record + speculative cut list + candidates of one shard (absolute
     positions).  Mirrors dsx_shard_local (seam_cands_kernel /
-    seam_finalize_kernel)."""
+    seam_finalize_kernel).  `cands`: o.candidates(full, mn, av, mx), for a
+    caller that takes many shards of one blob (a window at p reads 48 bytes
+    back, which the 64-byte halo below holds: the shard's candidates are the
+    blob's); a shard that ends the blob then takes its chain from the C chain
+    rule, which test_oracle_golden pins against Chunker.Next."""
     is_last = start + length == total
-    lo = max(0, start - 64)
-    c = o.candidates(full[lo:start + length], mn, av, mx) + lo  # halo for windows
+    if cands is None:
+        lo = max(0, start - 64)
+        c = o.candidates(full[lo:start + length], mn, av, mx) + lo  # halo for windows
+    else:
+        c = cands[cands <= start + length]
     c = c[(c > start) & (c >= 48)]
-    cuts = spec_chain(c, start, mn, mx, total, start + length, is_last)
+    if cands is not None and is_last:
+        s0 = np.uint64(start)
+        cuts = [] if length == 0 else (o.chain(c - s0, length, mn, mx) + s0).tolist()
+    else:
+        cuts = spec_chain(c, start, mn, mx, total, start + length, is_last)
     wend = start + min(length, 32 * mx)
-    wc = [int(x) for x in c if x <= wend]
+    wc = c[c <= wend][:max_cands + 1].tolist()
     if len(wc) > max_cands:
         wend = wc[max_cands - 1]
         wc = wc[:max_cands]

@@ -30,7 +30,7 @@ for i in range(3):
     desync_amd.cut_device(t.data_ptr(), n, avg // 4, avg, avg * 4, ctx=ctx)
 st = ctx.stats()
 st_scan_ms, st_stitch_ms = st.scan_ms, st.stitch_ms
-print(f"stats: chunks {st.chunks} candidates {st.candidates} repaired {st.repaired_segments} "
+print(f"stats: chunks {st.chunks} repaired {st.repaired_segments} "
       f"dense {st.dense_fallbacks}")
 ns, nw = ctypes.c_uint64(), ctypes.c_uint64()
 _lib.check(L.dsx_debug_trace(ctx.h, None, 0, ctypes.byref(ns), ctypes.byref(nw)), ctx.h)
