@@ -16,6 +16,7 @@ mirror of the reference's Go API for that path:
     Info, IDSet, dedup (chunk-ID sets on the GPU)           (cmd/desync/info.go, fileseed.go)
     NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
     DeviceStore, ChopBlob, ChunkMissing (a chunk store in HBM)  (store.go, local.go, chop.go, errors.go)
+    DeviceStore.Prune, RemoveChunk, Verify(repair=True)     (local.go, cmd/desync/prune.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """

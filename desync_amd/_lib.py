@@ -61,7 +61,7 @@ EXPORTS = (
     "dsx_host_sha512_256", "dsx_idset_create", "dsx_idset_destroy", "dsx_idset_count", "dsx_dedup",
     "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble", "dsx_store_create", "dsx_store_destroy",
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
-    "dsx_store_resolve", "dsx_store_verify",
+    "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -74,6 +74,7 @@ DSX_SRC_NULL = -1          # dsx_plan_seg_t.source: the null seed
 DSX_SRC_STORE = -2         # ... the packed store buffer
 DSX_STORE_DEVICE = 128
 DSX_ASSEMBLE_UNALIGNED = 256
+DSX_PRUNE_REMOVE = 512
 DSX_ASSEMBLE_TILE = 65536
 
 
@@ -135,6 +136,14 @@ class StorePutTotals(ctypes.Structure):
 
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("total", "stored", "stored_bytes", "present", "repeats")]
+
+
+class StorePruneTotals(ctypes.Structure):
+    """dsx_store_prune_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("entries", "kept", "kept_bytes", "removed", "removed_bytes", "moved", "moved_bytes",
+                 "unmatched")]
 
 
 class PlanSeed(ctypes.Structure):
@@ -306,6 +315,7 @@ def lib():
             "dsx_store_entries": (i32, [vp, vp, u64, u64, vp, vp, u32]),
             "dsx_store_resolve": (i32, [vp, vp, vp, u64, vp, u64, P(u64), P(u64), P(u32), u32]),
             "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
+            "dsx_store_prune": (i32, [vp, vp, vp, u64, u64, P(StorePruneTotals), u32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)

@@ -888,6 +888,10 @@ int run_index(dsx_ctx* c, const dsx_params_t* p, int algo, uint64_t len, FillFn 
     // current window's confirmed chunks are hashed first.
     auto partial = [&](int err) -> int {
       drain(c, pf, err);
+      // No piece of this call was scanned: the device chain state is another
+      // call's, or in a fresh context was never written, and a snapshot of it
+      // would send the digest over chunks that do not exist.
+      if (c->init_pending) return err;
       if (algo >= 0) {
         hipLaunchKernelGGL(state_snapshot_kernel, dim3(1), dim3(64), 0, c->stream,
                            (const DevState*)c->state.p, c->idx_snap.p + 2 * (w + 1));

@@ -8,13 +8,17 @@
 
 struct dsx_ctx;
 
-// A chunk store (include/dsx.h, dsx_store_t): an append-only arena of chunk
-// bytes keyed by chunk ID.  Entry e is the e-th chunk appended: its ID is
-// ids[32 e], its bytes arena[ends[e-1], ends[e]) (ends[-1] = 0).  slots[s] is
+// A chunk store (include/dsx.h, dsx_store_t): a tightly packed arena of chunk
+// bytes keyed by chunk ID.  Entry e is the e-th chunk appended that a prune has
+// not removed: its ID is ids[32 e], its bytes arena[ends[e-1], ends[e])
+// (ends[-1] = 0).  slots[s] is
 // 0xFFFFFFFF (empty) or an entry number; the table has idset_table_cap(
 // max_chunks) slots, so its load factor never exceeds 0.5.  Nothing is ever
 // reallocated: the arena's address holds for the store's life.  chunks and
-// bytes are host copies of the fill state, advanced after each accepted put.
+// bytes are host copies of the fill state, advanced after each accepted put and
+// set back by a prune.  broken: a prune failed between its first and its last
+// write to the store, which is then neither the old nor the new one; every call
+// but dsx_store_destroy refuses it (DSX_E_STATE).
 struct dsx_store {
   dsx_ctx* ctx = nullptr;
   DevBuf<uint8_t> ids;     // max_chunks * 32 bytes
@@ -23,22 +27,29 @@ struct dsx_store {
   DevBuf<uint8_t> arena;   // arena_bytes
   uint64_t max_chunks = 0, arena_bytes = 0, cap = 0, salt = 0;
   uint64_t chunks = 0, bytes = 0;
+  bool broken = false;
 };
 
 // The scratch of the store's calls.  Grows once, reused.  (The call's own ID
 // table and the staged copies of host arguments are IdsetScratch's.)
 struct StoreScratch {
-  DevBuf<uint8_t> flag;               // put: new[i]; verify: mismatch[e]
-  DevBuf<unsigned long long> blk;     // put: {chunks, bytes} per workgroup, then their prefix sums
+  DevBuf<uint8_t> flag;               // put: new[i]; verify: mismatch[e]; prune: keep[e]
+  DevBuf<unsigned long long> blk;     // put, prune: {chunks, bytes} per workgroup, then their prefix sums
   DevBuf<unsigned long long> tot;     // kStoreCounters words
-  DevBuf<unsigned long long> segs;    // put: the new chunks as AsmSeg records (3 words each)
+  DevBuf<unsigned long long> segs;    // put: the new chunks, prune: the survivors, as AsmSeg records (3 words each)
   DevBuf<unsigned long long> offs, sizes;  // locate / resolve: staged outputs
   DevBuf<uint32_t> idx;               // resolve: the store segments' target positions
   DevBuf<uint8_t> vids;               // verify: the computed IDs
+  DevBuf<uint8_t> pids;               // prune: the survivors' IDs, packed ...
+  DevBuf<unsigned long long> pends;   // ... and their new ends (copied over the store's after the arena moved)
+  DevBuf<uint8_t> bounce;             // prune: one window of the compacted arena
   std::vector<dsx_store*> live;       // the context's stores
 };
 
-constexpr int kStoreCounters = 4;  // stored, stored_bytes, present, error word (put); [0]: a count (others)
+// put: stored, stored_bytes, present, error word; prune: kept, kept_bytes,
+// UINT64_MAX - the first removed byte's offset (0: none), -, moved, moved_bytes;
+// others: [0] a count
+constexpr int kStoreCounters = 6;
 
 uint64_t store_device_bytes(const dsx_ctx* c);  // scratch + live stores
 void store_release(dsx_ctx* c);                 // frees both (dsx_ctx_destroy)

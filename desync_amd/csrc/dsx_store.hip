@@ -1,14 +1,16 @@
 // dsx_store.hip -- a chunk store in HBM (store.go:21-33, local.go,
-// chunkstorage.go): an append-only, deduplicating arena of chunk bytes keyed
+// chunkstorage.go): a deduplicating, tightly packed arena of chunk bytes keyed
 // by chunk ID, filled from a resident blob without a host round trip per
-// chunk and read in place by dsx_assemble.  The counterpart of a LocalStore
-// with Uncompressed: true (store.go:98-99).
+// chunk, read in place by dsx_assemble and pruned in place (PruneStore.Prune,
+// local.go:163-202).  The counterpart of a LocalStore with Uncompressed: true
+// (store.go:98-99).
 //
-// Layout (dsx_store.h): entry e is the e-th chunk appended; ids[32 e] is its
-// ID, arena[ends[e-1], ends[e]) its bytes.  The ID table is dsx_idset.hip's,
-// with entry numbers for positions: a full slot never changes.  Capacity is
-// fixed at creation, so the arena's address is stable and dsx_assemble can be
-// handed it as the store buffer.
+// Layout (dsx_store.h): entry e is the e-th chunk appended that no prune has
+// removed; ids[32 e] is its ID, arena[ends[e-1], ends[e]) its bytes.  The ID
+// table is dsx_idset.hip's, with entry numbers for positions: between two
+// prunes a full slot never changes.  Capacity is fixed at creation, so the
+// arena's address is stable and dsx_assemble can be handed it as the store
+// buffer.
 //
 // A put is a fixed sequence of launches on the context's stream:
 //   select  the call's own table (idset_insert_kernel), then one lane per
@@ -29,7 +31,23 @@
 // would read an entry another lane of the same launch is still writing.
 // No lane waits for another; the probe loops are bounded by the capacity.
 //
-// Out of scope: removing chunks, prune and compaction; growing a store;
+// A prune is the put turned around (DESIGN.md 4.7 has the safety argument):
+//   mark     the call's own table over ids[], then one lane per entry: keep[e],
+//            the totals, {kept entries, kept bytes} per workgroup;
+//   scan     the put's;
+//   (the host reads the totals; nothing removed: the call returns)
+//   compact  each survivor's new entry number and arena offset, as the append
+//            finds them; its ID, its new end and a gather record go to scratch;
+//   move     window by window over the destination [first removed byte, new
+//            used): assemble_kernel gathers a window's bytes from their old
+//            places into a bounce buffer, a copy writes the buffer over the
+//            window.  Every byte moves left or stays, so what a window's
+//            write-back destroys has been read by this or an earlier window,
+//            and what a later window needs lies behind it;
+//   rebuild  the new IDs and ends are copied over the store's, the table is
+//            cleared and every survivor claims a slot as the append does.
+//
+// Out of scope: growing a store;
 // compression and encryption converters; persistence (dsx_store_entries plus
 // the arena are enough for a caller to save and reload one); use from a
 // second context or GPU.
@@ -225,6 +243,124 @@ __global__ __launch_bounds__(kStoreThreads) void store_compare_kernel(const uint
   if ((threadIdx.x & 63) == 0 && bb) atomicAdd(n_bad, (u64)__popcll(bb));
 }
 
+struct PruneArgs {
+  const uint8_t* ids;     // the call's IDs ...
+  const uint32_t* slots;  // ... and the table over them
+  u64 n, mask, salt;
+  u64 invert;             // DSX_PRUNE_REMOVE: ids[] names the entries to drop
+  const uint8_t* st_ids;  // the store before the prune
+  const uint64_t* st_ends;
+  u64 st_n;
+  const uint8_t* arena;
+  uint8_t* flag;       // keep[e]
+  u64* blk;            // {kept entries, kept bytes} per workgroup
+  u64* tot;            // [kStoreCounters]
+  uint8_t* new_ids;    // [kept], written by the compaction
+  uint64_t* new_ends;  // [kept]
+  AsmSeg* segs;        // [kept]
+  u64 n_keep;          // the total the host read: the compaction's ranks stay below it
+};
+
+// One lane per entry: keep[e] = the entry's ID is among the call's (is not,
+// with invert).  tot[2] takes UINT64_MAX - the lowest offset of a removed entry
+// that has bytes: in front of that offset no byte moves.
+__global__ __launch_bounds__(kStoreThreads) void store_mark_kernel(PruneArgs a) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool keep = false;
+  u64 size = 0, gone_at = 0;
+  if (e < a.st_n) {
+    const bool named = idset_find(a.ids, a.n, a.slots, a.mask, a.salt, load_id(a.st_ids, e)) != kEmpty;
+    keep = named != (a.invert != 0);
+    const u64 lo = e ? a.st_ends[e - 1] : 0, hi = a.st_ends[e];
+    if (keep) size = hi - lo;
+    else if (hi > lo) gone_at = UINT64_MAX - lo;
+    a.flag[e] = keep ? 1 : 0;
+  }
+  const u64 bk = __ballot(keep);
+  const u64 bytes = wave_sum(size);
+#pragma unroll
+  for (int o = 32; o; o >>= 1) gone_at = std::max<u64>(gone_at, __shfl_down(gone_at, o, 64));
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    if (bk) atomicAdd(&a.tot[0], (u64)__popcll(bk));
+    if (bytes) atomicAdd(&a.tot[1], bytes);
+    if (gone_at) atomicMax(&a.tot[2], gone_at);
+    w_cnt[wave] = (u64)__popcll(bk);
+    w_bytes[wave] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 cnt = 0, by = 0;
+#pragma unroll
+    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
+    a.blk[2 * (u64)blockIdx.x] = cnt;
+    a.blk[2 * (u64)blockIdx.x + 1] = by;
+  }
+}
+
+// One lane per entry, the grid of store_mark_kernel, after the scan: survivor e
+// becomes entry `rank` at arena offset `off`.  The new IDs and ends go to
+// scratch (written in place they would overwrite entries another lane of this
+// launch still has to read); every survivor leaves a gather record, those in
+// front of the first removed byte with src == the place they already have.
+__global__ __launch_bounds__(kStoreThreads) void store_compact_kernel(PruneArgs a) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  bool keep = false;
+  u64 size = 0, old = 0;
+  if (e < a.st_n && a.flag[e]) {
+    keep = true;
+    old = e ? a.st_ends[e - 1] : 0;
+    size = a.st_ends[e] - old;
+  }
+  const u64 bk = __ballot(keep);
+  const u64 ib = wave_scan(size);
+  if (lane == 63) w_cnt[wave] = (u64)__popcll(bk), w_bytes[wave] = ib;
+  __syncthreads();
+  u64 rank = a.blk[2 * (u64)blockIdx.x] + (u64)__popcll(bk & ((1ull << lane) - 1));
+  u64 off = a.blk[2 * (u64)blockIdx.x + 1] + ib - size;
+#pragma unroll
+  for (int w = 0; w < kStoreWaves; ++w)
+    if ((uint32_t)w < wave) rank += w_cnt[w], off += w_bytes[w];
+  const bool moved = keep && off != old;
+  if (keep && rank < a.n_keep) {  // (always: the ranks are the scan of the flags the total counted)
+    const Id32 me = load_id(a.st_ids, e);
+    uint4* dst = reinterpret_cast<uint4*>(a.new_ids + 32 * rank);
+    dst[0] = me.lo;
+    dst[1] = me.hi;
+    a.new_ends[rank] = off + size;
+    AsmSeg g;
+    g.dst_off = off;
+    g.bytes = size;
+    g.src = a.arena + old;
+    a.segs[rank] = g;
+  }
+  const u64 bm = __ballot(moved);
+  const u64 mb = wave_sum(moved ? size : 0);
+  if (lane == 0) {
+    if (bm) atomicAdd(&a.tot[4], (u64)__popcll(bm));
+    if (mb) atomicAdd(&a.tot[5], mb);
+  }
+}
+
+// One lane per entry of the compacted store: the put's claim (no ID is
+// compared: the stored IDs differ from each other) into the cleared table.
+__global__ __launch_bounds__(kStoreThreads) void store_reclaim_kernel(const uint8_t* st_ids, u64 st_n,
+                                                                      uint32_t* st_slots, u64 st_mask,
+                                                                      u64 st_salt) {
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  if (e >= st_n) return;
+  u64 s = hash_id(load_id(st_ids, e), st_salt) & st_mask;
+  for (u64 step = 0; step <= st_mask; ++step, s = (s + 1) & st_mask) {
+    uint32_t cur = __hip_atomic_load(&st_slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur != kEmpty) continue;
+    cur = atomicCAS(&st_slots[s], kEmpty, (uint32_t)e);
+    if (cur == kEmpty) break;
+  }
+}
+
 }  // namespace dsx
 
 using namespace dsx;
@@ -232,6 +368,7 @@ using namespace dsx;
 namespace {
 
 constexpr uint64_t kStoreMaxN = 0xFFFFFFF0ull;
+constexpr uint64_t kPruneWindow = 256ull << 20;  // dsx_store_prune's window == 0 (DESIGN.md 4.7 has the sweep)
 
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
@@ -240,6 +377,11 @@ inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kStoreThreads - 1
 int invalid(dsx_ctx* c, const char* what) {
   c->err = what;
   return DSX_E_INVAL;
+}
+
+int broken(dsx_ctx* c) {
+  c->err = "the store is broken: a prune failed while it moved the arena; destroy it";
+  return DSX_E_STATE;
 }
 
 // [a, a + an) and [b, b + bn) share a byte
@@ -277,7 +419,7 @@ int stage_ids(dsx_ctx* c, const void* ids, uint64_t n, bool device, const uint8_
 uint64_t store_device_bytes(const dsx_ctx* c) {
   const StoreScratch& t = c->store;
   uint64_t b = t.flag.n + t.blk.n * 8 + t.tot.n * 8 + t.segs.n * 8 + t.offs.n * 8 + t.sizes.n * 8 +
-               t.idx.n * 4 + t.vids.n;
+               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n;
   for (const dsx_store* s : t.live) b += s->ids.n + s->ends.n * 8 + s->slots.n * 4 + s->arena.n;
   return b;
 }
@@ -286,6 +428,7 @@ void store_release(dsx_ctx* c) {
   StoreScratch& t = c->store;
   t.flag.release(), t.blk.release(), t.tot.release(), t.segs.release(), t.offs.release();
   t.sizes.release(), t.idx.release(), t.vids.release();
+  t.pids.release(), t.pends.release(), t.bounce.release();
   for (dsx_store* s : t.live) free_store(s);
   t.live.clear();
 }
@@ -337,6 +480,7 @@ extern "C" int dsx_store_destroy(dsx_ctx_t* c, dsx_store_t* s) {
 
 extern "C" int dsx_store_count(const dsx_store_t* s, dsx_store_counts_t* out) {
   if (!s || !out) return DSX_E_INVAL;
+  if (s->broken) return DSX_E_STATE;
   out->chunks = s->chunks;
   out->bytes = s->bytes;
   out->max_chunks = s->max_chunks;
@@ -346,6 +490,7 @@ extern "C" int dsx_store_count(const dsx_store_t* s, dsx_store_counts_t* out) {
 
 extern "C" int dsx_store_arena(const dsx_store_t* s, const void** d_arena, uint64_t* used) {
   if (!s) return DSX_E_INVAL;
+  if (s->broken) return DSX_E_STATE;
   if (d_arena) *d_arena = s->arena.p;
   if (used) *used = s->bytes;
   return DSX_OK;
@@ -360,6 +505,7 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
   if (totals) *totals = dsx_store_put_totals_t{};
   if ((flags & ~(f_ids | f_ends)) != 0) return invalid(c, "unknown flag bit");
   if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
   if (n > kStoreMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
   if (n && (!ids || !ends)) return invalid(c, "the IDs or the chunk ends are missing");
   if (len && !d_blob) return invalid(c, "the blob is missing");
@@ -486,6 +632,7 @@ extern "C" int dsx_store_locate(dsx_ctx_t* c, const dsx_store_t* s, const void* 
   if (n_missing) *n_missing = 0;
   if ((flags & ~(f_ids | f_out)) != 0) return invalid(c, "unknown flag bit");
   if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
   if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if (n && !ids) return invalid(c, "the IDs are missing");
   if (n == 0) return DSX_OK;
@@ -524,6 +671,7 @@ extern "C" int dsx_store_entries(dsx_ctx_t* c, const dsx_store_t* s, uint64_t fi
   if (!c || !s) return DSX_E_INVAL;
   if ((flags & ~DSX_OUT_DEVICE) != 0) return invalid(c, "unknown flag bit");
   if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
   if (first > s->chunks || n > s->chunks - first)
     return invalid(c, "first + n is beyond the store's entries");
   if (n == 0) return DSX_OK;
@@ -546,6 +694,7 @@ extern "C" int dsx_store_resolve(dsx_ctx_t* c, const dsx_store_t* s, const void*
   if (first_bad) *first_bad = 0xFFFFFFFFu;
   if ((flags & ~DSX_IDS_DEVICE) != 0) return invalid(c, "unknown flag bit");
   if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
   if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if ((n && !ids) || (nsegs && !segs)) return invalid(c, "the IDs or the segments are missing");
   try {
@@ -612,6 +761,7 @@ extern "C" int dsx_store_verify(dsx_ctx_t* c, const dsx_store_t* s, int algo, ui
   if (algo != DSX_DIGEST_SHA512_256 && algo != DSX_DIGEST_SHA256)
     return invalid(c, "algo names no digest");
   if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
   if (cap && !bad) return invalid(c, "the list of bad entries is missing");
   const uint64_t n = s->chunks;
   if (n == 0) return DSX_OK;
@@ -650,4 +800,155 @@ extern "C" int dsx_store_verify(dsx_ctx_t* c, const dsx_store_t* s, int algo, ui
   } catch (const std::bad_alloc&) {
     return DSX_E_NOMEM;
   }
+}
+
+// grow() without the headroom: prune's scratch is sized by its arguments
+template <class T>
+static hipError_t fit(dsx_ctx* c, DevBuf<T>& b, size_t n) {
+  if (b.p && b.n >= n) return hipSuccess;
+  if (b.p) {
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->copy_stream);
+    if (c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
+  }
+  return b.ensure(n);
+}
+
+extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, uint64_t n,
+                               uint64_t window, dsx_store_prune_totals_t* totals, uint32_t flags) {
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_rm = DSX_PRUNE_REMOVE;
+  if (!c || !s) return DSX_E_INVAL;
+  DSX_FLUSH_BEHIND(c);
+  if (totals) *totals = dsx_store_prune_totals_t{};
+  if ((flags & ~(f_ids | f_rm)) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
+  if (s->broken) return broken(c);
+  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n && !ids) return invalid(c, "the IDs are missing");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  IdsetScratch& t = c->idset;
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint64_t entries = s->chunks, T = DSX_ASSEMBLE_TILE;
+
+  // ---- mark, scan --------------------------------------------------------------
+  const uint8_t* d_ids = nullptr;
+  int rc = n ? stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids) : DSX_OK;
+  if (rc) return rc;
+  const uint32_t blocks = blocks_of(entries);
+  const uint64_t cap = idset_table_cap(n);
+  HIPCHK(c, grow(c, t.slots, cap));
+  HIPCHK(c, grow(c, t.tot, kIdsetCounters));
+  HIPCHK(c, grow(c, w.flag, entries));
+  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+  const uint64_t salt = idset_next_salt();
+  rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  PruneArgs a{};
+  a.ids = d_ids;
+  a.slots = t.slots.p;
+  a.n = n;
+  a.mask = cap - 1;
+  a.salt = salt;
+  a.invert = (flags & f_rm) ? 1 : 0;
+  a.st_ids = s->ids.p;
+  a.st_ends = s->ends.p;
+  a.st_n = entries;
+  a.arena = s->arena.p;
+  a.flag = w.flag.p;
+  a.blk = w.blk.p;
+  a.tot = w.tot.p;
+  if (blocks) {
+    hipLaunchKernelGGL(store_mark_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
+    HIPCHK(c, hipGetLastError());
+  }
+  // ---- the one wait before anything moves ---------------------------------------
+  u64 tot[kStoreCounters] = {}, distinct = 0;
+  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&distinct, t.tot.p, sizeof distinct, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const uint64_t kept = tot[0], kept_bytes = tot[1];
+  if (kept > entries || kept_bytes > s->bytes) return invalid(c, "the store's entries are inconsistent");
+  const uint64_t removed = entries - kept;
+  const uint64_t named = (flags & f_rm) ? removed : kept;  // the distinct IDs of ids[] the store held
+  if (totals) {
+    totals->entries = entries;
+    totals->kept = kept;
+    totals->kept_bytes = kept_bytes;
+    totals->removed = removed;
+    totals->removed_bytes = s->bytes - kept_bytes;
+    totals->unmatched = distinct - named;
+  }
+  if (!removed) return DSX_OK;
+
+  // ---- compact the metadata (into scratch) ---------------------------------------
+  uint64_t win = std::min<uint64_t>(window ? window : kPruneWindow, 1ull << 62);
+  win = (win + T - 1) / T * T;
+  win = std::min<uint64_t>(win, (s->arena_bytes + 15 + T) / T * T);  // (an arena's tiles: it never needs more)
+  const uint64_t first_off = tot[2] ? UINT64_MAX - tot[2] : kept_bytes;  // in front of it nothing moves
+  const bool moves = first_off < kept_bytes;
+  if (kept) {
+    HIPCHK(c, fit(c, w.pids, kept * 32));
+    HIPCHK(c, fit(c, w.pends, kept));
+    HIPCHK(c, grow(c, w.segs, 3 * kept));
+    if (moves) HIPCHK(c, fit(c, w.bounce, win));
+    a.new_ids = w.pids.p;
+    a.new_ends = (uint64_t*)w.pends.p;
+    a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
+    a.n_keep = kept;
+    hipLaunchKernelGGL(store_compact_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  // ---- move, rebuild: from the first write-back on the store is in between -------
+  auto rest = [&]() -> int {
+    if (kept && moves) {
+      // Windows are whole tiles of the gather's grid over the arena's addresses;
+      // a window's gather writes bounce[0, ..) through a pointer shifted so that
+      // arena offset D = ka T - skew lands on bounce.p (16-byte aligned, as D's
+      // address is: the bounce has the arena's grid).
+      const uint64_t skew = (uintptr_t)s->arena.p & 15;
+      const uint64_t k0 = (first_off + skew) / T, k1 = (kept_bytes + skew + T - 1) / T;
+      for (uint64_t ka = k0; ka < k1; ka += win / T) {
+        const uint64_t kb = std::min<uint64_t>(ka + win / T, k1);
+        const uint64_t lo = std::max<uint64_t>(first_off, ka * T > skew ? ka * T - skew : 0);
+        const uint64_t hi = std::min<uint64_t>(kb * T - skew, kept_bytes);
+        uint8_t* out = (uint8_t*)((uintptr_t)w.bounce.p + skew - ka * T);
+        const int r = assemble_launch(c, a.segs, kept, out, hi, lo, hi, false);
+        if (r) return r;
+        HIPCHK(c, hipMemcpyAsync(s->arena.p + lo, out + lo, hi - lo, hipMemcpyDeviceToDevice, st));
+      }
+    }
+    if (kept) {
+      HIPCHK(c, hipMemcpyAsync(s->ids.p, w.pids.p, kept * 32, hipMemcpyDeviceToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(s->ends.p, w.pends.p, kept * 8, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(s->slots.p, 0xFF, s->cap * sizeof(uint32_t), st));
+    if (kept) {
+      hipLaunchKernelGGL(store_reclaim_kernel, dim3(blocks_of(kept)), dim3(kStoreThreads), 0, st,
+                         (const uint8_t*)s->ids.p, (u64)kept, s->slots.p, (u64)(s->cap - 1),
+                         (u64)s->salt);
+      HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return DSX_OK;
+  };
+  rc = rest();
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    s->broken = true;
+    return rc;
+  }
+  s->chunks = kept;
+  s->bytes = kept_bytes;
+  if (totals) {
+    totals->moved = tot[4];
+    totals->moved_bytes = tot[5];
+  }
+  return DSX_OK;
 }

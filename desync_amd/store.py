@@ -1,20 +1,25 @@
 """A chunk store in HBM: what desync puts between the write and the read side.
 
 Reference interface:
-    Store, WriteStore                     (store.go:21-33)
+    Store, WriteStore, PruneStore         (store.go:21-39)
     LocalStore with Uncompressed: true    (local.go, store.go:98-99)
-    LocalStore.Verify                     (local.go:103-161)
+    LocalStore.Verify, with repair        (local.go:103-161)
+    LocalStore.RemoveChunk, Prune         (local.go:69-75, :163-202)
+    desync prune's merge of the indexes   (cmd/desync/prune.go:71-81)
     ChunkStorage.StoreChunk               (chunkstorage.go:44-67)
     ChopFile                              (chop.go:14-81)
     ChunkMissing                          (errors.go:5-17)
 
-:class:`DeviceStore` is an append-only, deduplicating arena of chunk bytes on
-the GPU, keyed by chunk ID (dsx_store_*).  It is filled from a
+:class:`DeviceStore` is a deduplicating, tightly packed arena of chunk bytes
+on the GPU, keyed by chunk ID (dsx_store_*).  It is filled from a
 blob resident in HBM by kernels (``put``: which chunks are new, where they go
 and the copy, without a host round trip per chunk) and read in place by
 dsx_assemble (:func:`desync_amd.AssembleBlob` with such a store fetches
-nothing through the host).  Its capacity is fixed when it is created.  Out of
-scope: removing chunks, growing, compression, persistence, a second context.
+nothing through the host).  ``Prune`` / ``RemoveChunk`` / ``Verify(repair=True)``
+remove chunks and compact the arena where it lies (dsx_store_prune), giving
+the room back to later puts.  Its capacity is fixed when it is created.  Out
+of scope: growing, copying between stores, compression, persistence, a second
+context.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ import numpy as np
 from . import _lib, digest
 from ._lib import DSX_ENDS_DEVICE, DsxError, lib
 from .errors import ChunkInvalid, ChunkMissing
-from .info import _ids_arg, _is_device
+from .info import _host_ids, _ids_arg, _is_device
 from .make import _digest_code
 
 OFF_NONE = 0xFFFFFFFFFFFFFFFF  # locate's offset of an ID the store does not hold
@@ -216,16 +221,19 @@ class DeviceStore:
                                            flags), self.ctx)
         return miss.value, wrong.value, bad.value
 
-    def Verify(self, algo=None):
+    def Verify(self, algo=None, repair=False):
         """LocalStore.Verify (local.go:103-161): re-hashes every stored chunk in
         the arena and returns the IDs of those that do not hash to their ID (an
         empty list for a sound store).  ``algo`` defaults to the package-global
-        Digest.  Nothing is removed (no repair)."""
+        Digest.  With ``repair`` the bad chunks are then removed, all in one
+        prune; without it nothing is removed."""
         with self._lock:
             bad = self.verify_entries(algo)
             if not bad:
                 return []
             ids, _ = self.entries()
+            if repair:
+                self._prune(ids[bad], remove=True)
             return [ids[e].tobytes() for e in bad]
 
     def verify_entries(self, algo=None):
@@ -237,6 +245,41 @@ class DeviceStore:
             _check(lib().dsx_store_verify(self.ctx.h, self.h, _digest_code(algo), bad.ctypes.data, n,
                                           ctypes.byref(n_bad)), self.ctx)
             return bad[:n_bad.value].tolist()
+
+    # ---- retention -------------------------------------------------------------------
+    def _prune(self, ids, remove=False, window=0, n=None):
+        iptr, n, flags, _keep = _ids_arg(ids, n)
+        if remove:
+            flags |= _lib.DSX_PRUNE_REMOVE
+        tot = _lib.StorePruneTotals()
+        with self._lock:
+            _check(lib().dsx_store_prune(self.ctx.h, self.h, ctypes.c_void_p(iptr), n, int(window),
+                                         ctypes.byref(tot), flags), self.ctx)
+        return {k: getattr(tot, k) for k, _ in _lib.StorePruneTotals._fields_}
+
+    def Prune(self, ids, window=0, n=None):
+        """PruneStore.Prune (local.go:163-202): removes every chunk whose ID is
+        not among ``ids`` and compacts the arena in place (dsx_store_prune).
+        ``ids`` is an iterable of 32-byte IDs, an ``(n, 32)`` array, device
+        memory (as for :class:`IDSet`), an :class:`Index`, or a list of
+        indexes, whose IDs are merged as ``desync prune`` merges them
+        (prune.go:71-81).  Returns the totals as a dict: entries, kept,
+        kept_bytes, removed, removed_bytes, moved, moved_bytes, unmatched.
+        Arena offsets taken before (``locate``, a resolved plan) are stale
+        afterwards.  ``window`` bounds the compaction's scratch (0: the default)."""
+        from .index import Index
+        if isinstance(ids, (list, tuple)) and ids and all(isinstance(i, Index) for i in ids):
+            ids = np.concatenate([_host_ids(i) for i in ids])
+        return self._prune(ids, False, window, n)
+
+    def RemoveChunk(self, cid):
+        """LocalStore.RemoveChunk (local.go:69-75): removes one chunk;
+        :class:`ChunkMissing` if the store does not hold it."""
+        cid = bytes(cid)
+        if len(cid) != 32:
+            raise ValueError("a chunk ID is 32 bytes")
+        if not self._prune([cid], remove=True)["removed"]:
+            raise ChunkMissing(cid)
 
     # ---- life ------------------------------------------------------------------------
     def close(self):

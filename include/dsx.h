@@ -29,6 +29,9 @@
  *   dsx_store_*          <- a LocalStore with Uncompressed: true (store.go:21-33,
  *                           :98-99, local.go) and ChunkStorage.StoreChunk
  *                           (chunkstorage.go:44-67), for chunks resident in HBM
+ *   dsx_store_prune      <- PruneStore.Prune (store.go:35-39, local.go:163-202)
+ *                           and RemoveChunk (local.go:69-75), compacting the
+ *                           arena in place
  *
  * Conventions (cgo-safe): plain pointers and sizes only; no pointer passed in
  * is retained after a call returns; every function returns 0 or a negative
@@ -611,17 +614,18 @@ int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
 /* ---- a chunk store in HBM: what lies between the write and the read side -------
  * The store desync puts between "which chunks are new" and "a plan plus the
  * chunks no seed holds" (store.go:21-33, local.go, chunkstorage.go), for blobs
- * that live in HBM: an append-only, deduplicating arena of chunk bytes keyed by
- * chunk ID, filled from a resident blob by kernels and read in place by
- * dsx_assemble.  The counterpart of a LocalStore with Uncompressed: true
- * (store.go:98-99).  DESIGN.md 4.7 has the layout and the put's launches.
+ * that live in HBM: a deduplicating, tightly packed arena of chunk bytes keyed
+ * by chunk ID, filled from a resident blob by kernels, read in place by
+ * dsx_assemble and pruned in place by dsx_store_prune.  The counterpart of a
+ * LocalStore with Uncompressed: true (store.go:98-99).  DESIGN.md 4.7 has the
+ * layout and the launches of a put and of a prune.
  * A store belongs to the context that created it: it is used with that context
  * only (a store of another context: DSX_E_INVAL with a dsx_last_error text),
  * its memory counts in that context's device_bytes, and dsx_ctx_destroy frees
  * the stores still alive.  Its capacity is fixed at creation and the arena is
- * never reallocated, so its address is stable for the store's life.
- * Out of scope: removing chunks, prune and compaction; growing a store;
- * compression and encryption converters; persistence (dsx_store_entries plus
+ * never reallocated, so its address is stable for the store's life (a prune
+ * moves chunks inside it).
+ * Out of scope: growing a store; copying between stores; compression and encryption converters; persistence (dsx_store_entries plus
  * the arena are enough for a caller to save and reload one); use from a second
  * context or GPU. */
 typedef struct dsx_store dsx_store_t;
@@ -710,6 +714,51 @@ int dsx_store_resolve(dsx_ctx_t *ctx, const dsx_store_t *store, const void *ids,
  * context's scratch (device_bytes). */
 int dsx_store_verify(dsx_ctx_t *ctx, const dsx_store_t *store, int algo, uint32_t *bad,
                      uint64_t cap, uint64_t *n_bad);
+
+/* PruneStore.Prune (store.go:35-39, local.go:163-202; desync prune merges the
+ * IDs of the indexes to keep, cmd/desync/prune.go:44-103) and, with
+ * DSX_PRUNE_REMOVE, RemoveChunk (local.go:69-75) for a list: what
+ * LocalStore.Verify with repair calls for each bad chunk (local.go:103-131). */
+#define DSX_PRUNE_REMOVE 512u  /* ids[] names the chunks to drop (RemoveChunk); default: the chunks to keep (Prune) */
+
+typedef struct dsx_store_prune_totals {
+    uint64_t entries;                 /* entries before the call */
+    uint64_t kept, kept_bytes;
+    uint64_t removed, removed_bytes;
+    uint64_t moved, moved_bytes;      /* kept entries whose arena offset changed, and their bytes */
+    uint64_t unmatched;               /* distinct IDs of ids[] the store did not hold */
+} dsx_store_prune_totals_t;           /* 64 bytes */
+
+/* ids[] holds n 32-byte IDs (host memory, or device memory with
+ * DSX_IDS_DEVICE; duplicates allowed).  An entry survives exactly when its ID is
+ * among them (n == 0 empties the store), or with DSX_PRUNE_REMOVE exactly when
+ * it is not (n == 0 changes nothing).  IDs the store does not hold are no
+ * error, as in the reference; totals->unmatched counts the distinct ones.
+ * Survivors keep their relative order and are renumbered 0 .. kept-1; the arena
+ * is tightly packed again, entry e at [ends[e-1], ends[e]), at the same address;
+ * arena bytes at and beyond the new `used` are unspecified.  Every store call
+ * answers for the compacted store, and the freed chunks and bytes are there for
+ * later puts.  Offsets taken before the prune are stale: a plan resolved with
+ * dsx_store_resolve, or the answers of dsx_store_locate, must be asked for
+ * again before dsx_assemble reads the arena through them.  Bytes in front of
+ * the first removed entry are not moved; if nothing is removed, no arena byte,
+ * entry or table slot is written.  The arena, the entries and the totals (host
+ * memory, may be NULL) are exact and the same on every run.
+ * window: the scratch in bytes the compaction may use (counted in device_bytes,
+ * grown once and reused), rounded up to a multiple of DSX_ASSEMBLE_TILE and
+ * never more than the arena needs; 0: the default, 256 MiB.  The arena is
+ * compacted window by window through that scratch, so each moved byte is read
+ * twice and written twice.
+ * Refused with DSX_E_INVAL and a dsx_last_error text before any device work:
+ * a store of another context, ids == NULL with n > 0, n > 0xFFFFFFF0, any flag
+ * bit other than DSX_IDS_DEVICE and DSX_PRUNE_REMOVE.
+ * Synchronous on the ctx stream: one host wait after the selection (the
+ * totals) and one at the end.  dsx_cancel does not interrupt it: a
+ * half-compacted arena is not a store.  If a HIP call fails after the first
+ * byte has moved, the store is broken: every later call on it but
+ * dsx_store_destroy returns DSX_E_STATE. */
+int dsx_store_prune(dsx_ctx_t *ctx, dsx_store_t *store, const void *ids, uint64_t n,
+                    uint64_t window, dsx_store_prune_totals_t *totals, uint32_t flags);
 
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
