@@ -1,10 +1,7 @@
-// dsx_api.cpp -- C ABI (include/dsx.h) and host engine of libdsx.so.
-//
-// The engine splits a blob into pieces, and per piece enqueues on the
-// context's HIP stream: scan (dsx_scan.hip) -> walk -> fixup -> gather
-// (dsx_stitch.hip).  The chain position is carried between pieces in device
-// memory (DevState.carry), so a multi-piece call needs no host round trip
-// until the end.  Reference interfaces replaced are listed in include/dsx.h.
+// dsx_api.cpp -- C ABI (include/dsx.h) of libdsx.so: parameters, contexts and
+// their settings, cut lists of device blobs, generators, chunk IDs, shards.
+// Every path runs through the host engine (dsx_engine.cpp).  Reference
+// interfaces replaced are listed in include/dsx.h.
 #include <hip/hip_runtime.h>
 #include <unistd.h>
 
@@ -102,45 +99,6 @@ extern "C" const char* dsx_strerror(int code) {
     case DSX_E_PEER: return "another rank failed (its seam record carries DSX_SEAM_ERROR)";
     default: return "unknown error";
   }
-}
-
-static TestConsts make_tc(const dsx_params_t* p) {
-  TestConsts tc;
-  tc.d = p->discriminator;
-  tc.dm1 = p->discriminator - 1u;
-  tc.inv = p->inverse_odd;
-  tc.qmax = p->qmax;
-  tc.qbias = p->qbias;
-  tc.rot = (uint32_t)p->rot;
-  tc.rcp = 1.0f / (float)p->discriminator;
-  // MODE 1 (is_cand in dsx_scan.hip): fma(h, 1/d, 1.5*2^23 - 1) puts
-  // round(h/d) - 1 + 0x400000 in the low mantissa bits; madc folds the
-  // 0x400000*d offset and the -1 back into the exact 24-bit check.
-  tc.c0 = 12582911.0f;
-  tc.madc = p->discriminator - 1u - (p->discriminator << 22);
-  // MODE 2 prefilter: with d = 2^k * dodd, h + 1 = d*m (1 <= m <= 2^32/d)
-  // gives t = (h+1)*inv - 1 = 2^k*m - 1 < 2^k*floor(2^32/d) = vmax (exact
-  // for odd d; for even d the rare path re-checks h % d == d-1)
-  const uint32_t k = (uint32_t)p->rot;
-  tc.tadd = p->inverse_odd - 1u;
-  tc.vmax = (uint32_t)(((1ull << 32) / p->discriminator) << k);
-  tc.dodd = p->discriminator >> k;
-  // scanl keeps ~h in the hash register (the same recurrence from ~0), so
-  // t + 1 = (h+1)*inv = (~h)*(2^32 - inv) is one v_mul_lo_u32
-  tc.ninv = 0u - p->inverse_odd;
-  tc.vmax1 = tc.vmax + 1u;
-  return tc;
-}
-
-// MODE 2 (multiply-inverse prefilter, DESIGN.md "Boundary test") for every d
-// that is not a power of two; MODE 1 (float, exact for 1024 < d < 2^22) or
-// MODE 0 (Go's form) otherwise
-static int pick_mode(const dsx_ctx* c, uint32_t d) {
-  if (c->force_mode >= 0 && c->force_mode <= 2) {
-    if (c->force_mode != 2 || (d & (d - 1u)) != 0) return c->force_mode;
-  }
-  if ((d & (d - 1u)) != 0) return 2;
-  return (d > 1024u && d < (1u << 22)) ? 1 : 0;
 }
 
 // --------------------------------------------------------------------------
@@ -469,675 +427,8 @@ extern "C" int dsx_stamps_end(dsx_ctx_t* c, dsx_scan_stamp_t* out, uint64_t cap,
 }
 
 // --------------------------------------------------------------------------
-// engine
+// cut lists of device-resident blobs (the engine: dsx_engine.cpp)
 // --------------------------------------------------------------------------
-
-// Stitch segment for a span of n bytes: max(mult * max, floor), doubled while
-// the span would have more than seg_target + 1 segments.  An 8 GiB piece gets
-// 2 MiB segments (4096-4097 of them): walk 31 + fixup 13.7 + gather 5.0 us
-// against 32.5 + 22.5 + 6.8 with 1 MiB, +0.45 % on the bench line; 4 MiB
-// lengthens the walks' chains (walk 55.6 us) (profiles/r04k).
-static uint64_t stitch_seg(const dsx_ctx* c, const dsx_params_t* p, uint64_t n) {
-  uint64_t seg = std::max<uint64_t>(c->seg_max_mult * p->max, c->seg_floor);
-  if (c->seg_target)
-    while ((n + seg - 1) / seg > c->seg_target + 1 && seg < (1ull << 26)) seg <<= 1;
-  return seg;
-}
-
-// The next scan launch initialises the device chain state (no memcpy).
-int reset_state(dsx_ctx* c, uint64_t carry) {
-  c->npiece_call = 0;
-  c->init_pending = true;
-  c->init_carry = carry;
-  return DSX_OK;
-}
-
-// Wait for the stream; the last fixup_kernel published the state into pinned
-// host memory.
-int read_state(dsx_ctx* c, HostState* out) {
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(out, (const void*)c->h_state, sizeof(HostState));
-  if (out->seq != c->piece_seq) {
-    c->err = "stale chain state (no piece completed)";
-    return DSX_E_INTERNAL;
-  }
-  return DSX_OK;
-}
-
-// Enqueue scan + stitch for one piece [P, P+len) whose bytes are at d_piece
-// (with `halo` readable bytes before it).
-int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo,
-                         uint64_t P, uint64_t len, bool is_last) {
-  const dsx_params_t* p = cc.p;
-  // ---- scan geometry: balance regions over the persistent grid ----
-  // lane segment S = 48*(4k-1): the warm-up round plus S/48 rounds fill k
-  // whole 4-round DMA batches
-  // scan configs: {waves per workgroup, rounds per DMA batch}
-  static const int kCfgWaves[6] = {8, 12, 16, 12, 8, 16};
-  static const int kCfgBR[6] = {2, 1, 1, 2, 2, 2};
-  // line-aligned scan (scanl_kernel) unless disabled, on the dense path, or
-  // when the grid origin P - delta would precede position 0
-  const uint32_t delta = (uint32_t)((uintptr_t)d_piece & (kLine - 1));
-  const bool line = c->scan_line && !cc.dense && P >= delta;
-  const int W = line ? c->scanl_waves : kCfgWaves[c->scan_cfg];
-  const int cfgBR = kCfgBR[c->scan_cfg];
-  const bool split = c->scan_stream != c->stream;
-  const int ncu_scan = c->ncu - (split ? c->stitch_cus : 0);  // CUs of the scan's mask
-  const uint64_t slots_total = (uint64_t)ncu_scan * W;         // wave slots
-  const uint64_t span = line ? len + delta : len;       // grid bytes
-  uint32_t S, LS;
-  uint32_t batches;
-  if (cc.dense) {
-    S = kDenseS;
-    LS = S;
-  } else if (line) {
-    // S = 384*m: about regions_per_slot regions per wave slot
-    const uint64_t lanes_min = slots_total * 64 * (uint64_t)c->regions_per_slot;
-    const uint64_t per_lane = (span + lanes_min - 1) / lanes_min;
-    const uint64_t rounds_needed = (per_lane + kLineLaneMax - 1) / kLineLaneMax;
-    const uint64_t s = (span + rounds_needed * lanes_min - 1) / (rounds_needed * lanes_min);
-    uint64_t m = (s + 3 * kLine - 1) / (3 * kLine);
-    // lane segments longer than the target lose HBM efficiency (lane stride
-    // 33 KB: 4.85 TB/s staging vs 6.24 TB/s at 8448 B, tools/ubench_staging.hip);
-    // bigger pieces take more regions per wave slot from the work queue
-    // (up to two trips past the target when that keeps every region in the
-    // first pass: a second pass for a few regions costs a whole region time)
-    const uint64_t mcap = c->lane_target / (3 * kLine);
-    if (m > mcap + mcap / 4 || rounds_needed > 1) m = std::min<uint64_t>(m, mcap);
-    m = std::max<uint64_t>(1, std::min<uint64_t>(m, kLineLaneMax / (3 * kLine)));
-    S = (uint32_t)(3 * kLine * m);
-    if (c->lane_bytes_override && c->lane_bytes_override % (3 * kLine) == 0 &&
-        c->lane_bytes_override <= kLineLaneMax)
-      S = c->lane_bytes_override;
-    LS = kLaneSlots;
-  } else {
-    // about regions_per_slot regions per wave slot (dynamic queue balances
-    // them), more if a lane segment would exceed kMaxLaneBytes
-    const uint64_t lanes_min = slots_total * 64 * (uint64_t)c->regions_per_slot;
-    const uint64_t per_lane = (len + lanes_min - 1) / lanes_min;
-    const uint64_t rounds_needed = (per_lane + kMaxLaneBytes - 1) / kMaxLaneBytes;
-    uint64_t s = (len + rounds_needed * lanes_min - 1) / (rounds_needed * lanes_min);
-    const uint64_t BR = (uint64_t)cfgBR;
-    uint64_t kb = (s / kRound + 1 + BR - 1) / BR;  // batches
-    if (kb < 4) kb = 4;
-    while (kRound * (BR * kb - 1) > kMaxLaneBytes) --kb;
-    s = (uint64_t)kRound * (BR * kb - 1);
-    if (c->lane_bytes_override && (c->lane_bytes_override / kRound + 1) % BR == 0)
-      s = c->lane_bytes_override;
-    S = (uint32_t)s;
-    LS = kLaneSlots;
-  }
-  batches = line ? S / (3 * kLine) : (S / kRound + 1) / (uint32_t)cfgBR;
-  const uint64_t region_bytes = 64ull * S;
-  uint64_t nregions = len == 0 ? 0 : (span + region_bytes - 1) / region_bytes;
-  // Two region sizes (DSX_TAIL_SPLIT = k > 1, default 4; line scan, pieces of
-  // at least three big regions per wave slot): the last ~one big region's
-  // worth of bytes per wave slot is cut into regions with k times shorter lane
-  // segments, so the waves that drain the work queue last hold small regions
-  // (DSX_TAIL_MULT = j: j big regions' worth per wave slot).  On the 8 GiB
-  // pieces the waves end together (wave_busy 0.947 -> 0.98) and the scan is
-  // 1 % faster; k = 2, 6, 8 and j = 2 less (profiles/r04d, r04e, r04g, r04aa).
-  // (k = 3 was the default while every lane read a warm-up line: k = 4 read
-  // 1.021 x the input against 1.018; since the warm-up handoff only lane 0 of
-  // a region does, and k = 4 is 0.4-0.5 % ahead, profiles/r04ab.)
-  uint64_t nbig = nregions, S2 = 0;
-  if (line && !cc.dense && !cc.behind && c->tail_split > 1 && len > 0) {
-    const uint64_t m = S / (3 * kLine), m2 = std::max<uint64_t>(1, m / (uint64_t)c->tail_split);
-    const uint64_t tail = slots_total * region_bytes * (uint64_t)c->tail_mult;
-    if (m2 < m && span >= 3 * tail) {
-      const uint64_t rb2 = 64ull * 3 * kLine * m2;
-      nbig = (span - tail) / region_bytes;
-      nregions = nbig + (span - nbig * region_bytes + rb2 - 1) / rb2;
-      S2 = 3 * kLine * m2;
-    }
-  }
-  const uint64_t nlanes = nregions * 64;
-  uint32_t rcap;
-  if (cc.dense) {
-    rcap = 64u * S;
-  } else {
-    const double expct = (double)region_bytes / (double)p->discriminator;
-    rcap = (uint32_t)std::min<double>(64.0 * S, 4.0 * expct + 64.0);
-    rcap = (rcap + 63u) & ~63u;
-  }
-  c->last_region_bytes = region_bytes;
-  c->last_nregions = (uint32_t)nregions;
-  c->last_region_cap = rcap;
-  c->last_nbig = (uint32_t)nbig;
-  c->last_region_bytes2 = S2 ? 64ull * S2 : 0;
-  HIPCHK(c, grow(c, c->lane_slot, nlanes * LS));
-  // region lists: the context's scratch, or (cc.keep: shards) buffers of
-  // their own that outlive the call, so a re-walk can re-run the stitch
-  // without scanning the bytes again
-  uint32_t *rcnt, *rlist;
-  KeptPiece* kp = nullptr;
-  if (cc.keep) {
-    if (c->sh.nkept == cc.keep->size()) cc.keep->emplace_back();
-    kp = &(*cc.keep)[c->sh.nkept++];
-    HIPCHK(c, grow(c, kp->cnt, nregions));  // (reused across runs: grows once)
-    HIPCHK(c, grow(c, kp->list, nregions * rcap));
-    rcnt = kp->cnt.p;
-    rlist = kp->list.p;
-  } else {
-    // split streams: two region-list sets, so the next piece's scan writes
-    // one while this piece's stitch reads the other
-    // (and stitch behind: the next scan writes one while its tasks walk
-    // the other)
-    const bool second = (split || cc.behind) && (c->piece_seq + 1) % 2 == 1;
-    auto& bc = second ? c->region_cnt2 : c->region_cnt;
-    auto& bl = second ? c->region_list2 : c->region_list;
-    HIPCHK(c, grow(c, bc, nregions));
-    HIPCHK(c, grow(c, bl, nregions * rcap));
-    rcnt = bc.p;
-    rlist = bl.p;
-  }
-  c->last_rcnt = rcnt;
-  c->last_rlist = rlist;
-  // stitch behind: this call's segment set (by piece parity), and the tasks
-  // of the calls behind it that this scan carries
-  dsx_ctx::Behind me;
-  TaskArgs tb{};
-#if DSX_DIAG
-  if (cc.behind) {
-    const bool second = (c->piece_seq + 1) % 2 == 1;
-    const uint64_t seg = stitch_seg(c, p, len);
-    const uint64_t nseg = (len + seg - 1) / seg;
-    const uint32_t scap = (uint32_t)(seg / p->min + 3);
-    auto& bs = second ? c->seg_info2 : c->seg_info;
-    auto& bt = second ? c->stage2 : c->stage;
-    auto& bp = second ? c->spec2 : c->spec;
-    if (bs.n < nseg || bt.n < nseg * scap || bp.n < nseg * scap) {
-      // the call two back may still have to finish from this set: launch it
-      // on its own before the set is reallocated
-      int rc = flush_behind(c);
-      if (rc) return rc;
-      HIPCHK(c, grow(c, bs, nseg));
-      HIPCHK(c, grow(c, bt, nseg * scap));
-      HIPCHK(c, grow(c, bp, nseg * scap));
-    }
-    // segments per walk task (one lane each, up to 63): the task's
-    // candidates fill at most half of its LDS on average
-    const double exp_per_seg = (double)seg / (double)p->discriminator + 8.0;
-    me.wseg = (uint32_t)std::max(1.0, std::min(32.0, std::floor(kTaskCand / (2.0 * exp_per_seg)) - 1.0));
-    me.fseg = 32;
-    me.nw = (uint32_t)((nseg + me.wseg - 1) / me.wseg);
-    me.nf = (uint32_t)((nseg + me.fseg - 1) / me.fseg);
-    me.w.min = p->min;
-    me.w.max = p->max;
-    me.w.L = len;
-    me.w.seg = seg;
-    me.w.nseg = (uint32_t)nseg;
-    me.w.scap = scap;
-    me.w.seg_info = bs.p;
-    me.w.stage = bt.p;
-    me.w.spec = bp.p;
-    me.f.seg_info = bs.p;
-    me.f.stage = bt.p;
-    me.f.spec = bp.p;
-    me.f.nseg = (uint32_t)nseg;
-    me.f.scap = scap;
-    me.f.out = cc.d_out;
-    me.f.out_cap = cc.out_cap;
-    me.f.host_state = c->h_cur;
-    for (const auto& b : c->behind) {
-      if (!b.walked) {
-        tb.w = b.w;
-        tb.nw = b.nw;
-        tb.wseg = b.wseg;
-      } else {
-        tb.f = b.f;
-        tb.nf = b.nf;
-        tb.fseg = b.fseg;
-      }
-    }
-  }
-#endif
-  const uint64_t seq = ++c->piece_seq;
-  const int par = (int)(seq & 1);
-  hipStream_t ss = c->scan_stream;
-
-  ScanArgs sa{};
-  sa.base = d_piece;
-  sa.halo = halo;
-  sa.piece_abs = P;
-  sa.len = len;
-  sa.lane_bytes = S;
-  sa.batches = batches;
-  sa.nregions = (uint32_t)nregions;
-  if (S2) {
-    sa.nbig = (uint32_t)nbig;
-    sa.lane_bytes2 = (uint32_t)S2;
-    sa.batches2 = (uint32_t)(S2 / (3 * kLine));
-  }
-  sa.region_cap = rcap;
-  sa.tc = make_tc(p);
-  sa.min_pos = cc.min_pos;
-  sa.lane_slots = LS;
-  sa.pf_batches = (uint32_t)c->prefetch_batches;
-  sa.lane_slot = c->lane_slot.p;
-  sa.region_cnt = rcnt;
-  sa.region_list = rlist;
-  // overflow word and queue counters: slot seq % 4; the scan zeroes the next
-  // piece's slot (the stitch of the previous piece may still read its own)
-  sa.overflow = c->overflow.p + (seq % kQueueSlots);
-  sa.overflow_next = c->overflow.p + ((seq + 1) % kQueueSlots);
-  sa.queue = c->overflow.p + 32 + 256 * (seq % kQueueSlots);
-  sa.queue_next = c->overflow.p + 32 + 256 * ((seq + 1) % kQueueSlots);
-  sa.wave_major = c->wave_major ? (cc.behind ? 2u : 1u) : 0u;
-  sa.nt_loads = (uint32_t)c->scan_nt;
-  if (c->pub_host) {  // the previous queued piece's state, published by this scan
-    sa.pub_state = c->state.p;
-    sa.pub_host = c->pub_host;
-    sa.pub_seq = c->pub_seq;
-    c->pub_host = nullptr;
-  }
-  tb.counter = sa.queue + 1;  // (zeroed by the previous scan, with the queue)
-  tb.farrive = sa.queue + 2;
-
-#if DSX_DIAG
-  if (cc.behind) {
-    // the ring advances with fused calls only: the slot was last read by the
-    // scan of the fused call kTaskRing (16) fused calls ago, which completed
-    // before the call kQueueDepth (8) queued calls ago was collected (a
-    // non-fused multi-piece call between them does not move the index)
-    TaskArgs* slot = c->h_tasks + (c->fuse_seq++ % dsx_ctx::kTaskRing);
-    *slot = tb;
-    sa.tasks = slot;
-  }
-#endif
-  if (line) {
-    // region 0's descriptor: the warm-up line unless it would start before
-    // the readable bytes (then the 16-B step at or below base - min(halo, 48))
-    const uint64_t hmin = std::min<uint64_t>(halo, kRound);
-    sa.delta = delta;
-    sa.shift0 = halo >= (uint64_t)delta + kLine
-                    ? 0u
-                    : (uint32_t)(16 * (((uint64_t)kLine + delta - hmin) / 16));
-  }
-  c->last_grid_P = line ? P - delta : P;
-  if (c->stamping && line && c->stamp_meta.size() < c->stamp_cap && W == c->scanl_waves) {
-    sa.stamp = c->stamp_ring.p + c->stamp_slots * kStampWords * c->stamp_meta.size();
-    c->stamp_meta.emplace_back(seq, len);
-  }
-  if (c->scan_trace && line) {
-    c->trace_n = (uint64_t)c->ncu * W;
-    const uint64_t slot_words = kScanTraceWords * c->trace_n + 10 * 65536ull;
-    HIPCHK(c, grow(c, c->trace, (c->trace_keep ? 4 : 1) * slot_words));
-    c->trace_base = c->trace_keep ? (seq % 4) * slot_words : 0;
-    // (stitch behind: 6 task words per wave slot follow, read as walk records)
-    const uint64_t tw = cc.behind ? 6 * c->trace_n : 0;
-    HIPCHK(c, hipMemsetAsync(c->trace.p + c->trace_base, 0, (kScanTraceWords * c->trace_n + tw) * sizeof(uint64_t), ss));
-    sa.trace = c->trace.p + c->trace_base;
-    if (cc.behind) c->trace_walk_n = (tw + 9) / 10;
-  }
-  const uint32_t pi = c->npiece_call++;
-  while (c->pev.size() < 3 * (size_t)(pi + 1)) {
-    hipEvent_t e;
-    HIPCHK(c, hipEventCreate(&e));
-    c->pev.push_back(e);
-  }
-  // the region lists this scan writes were read by the stitch two pieces ago
-  if (split) HIPCHK(c, hipStreamWaitEvent(ss, c->ev_stitch[par], 0));
-  if (c->timing) HIPCHK(c, hipEventRecord(c->pev[3 * pi], ss));
-#if DSX_DIAG
-  if (getenv("DSX_NOOP_BEFORE_SCAN")) hipLaunchKernelGGL(noop_kernel, dim3(1), dim3(64), 0, ss);
-#endif
-  {
-    const uint64_t need_wg = std::max<uint64_t>(1, (nregions + W - 1) / W);
-    // (stitch behind: every CU, so the wave slots beyond the regions -- spread
-    // over the grid by the wave-major order -- run the tasks from the start)
-    const uint32_t grid = cc.behind ? (uint32_t)ncu_scan
-                                    : (uint32_t)std::min<uint64_t>(need_wg, (uint64_t)ncu_scan);
-    const dim3 g(grid), b(W * kWave);
-    const int mode = pick_mode(c, p->discriminator);
-#if DSX_DIAG
-#define DSX_ABLATE(K, ...)                                                                 \
-  if (c->variant == 1) hipLaunchKernelGGL((K<2, 1, __VA_ARGS__>), g, b, 0, ss, sa); \
-  else if (c->variant == 3) hipLaunchKernelGGL((K<2, 3, __VA_ARGS__>), g, b, 0, ss, sa); \
-  else if (c->variant == 4) hipLaunchKernelGGL((K<2, 4, __VA_ARGS__>), g, b, 0, ss, sa); \
-  else
-// (the piece's region geometry picks TWO, as for the exact kernel: a one-size
-// instantiation over a two-size region list reads past the piece)
-#define DSX_LV(K, V, ...)                                                                  \
-  do {                                                                                     \
-    if (sa.lane_bytes2) hipLaunchKernelGGL((K<2, V, __VA_ARGS__, false, true>), g, b, 0, ss, sa); \
-    else hipLaunchKernelGGL((K<2, V, __VA_ARGS__, false, false>), g, b, 0, ss, sa);      \
-  } while (0)
-#define DSX_ABLATEL(K, ...)                                                                \
-  if (c->variant == 1) DSX_LV(K, 1, __VA_ARGS__);                                        \
-  else if (c->variant == 3) DSX_LV(K, 3, __VA_ARGS__);                                   \
-  else if (c->variant == 4) DSX_LV(K, 4, __VA_ARGS__);                                   \
-  else if (c->variant == 7 && mode == 2) DSX_LV(K, 7, __VA_ARGS__);                      \
-  else if (c->variant == 8 && mode == 2) DSX_LV(K, 8, __VA_ARGS__);                      \
-  else if (c->variant == 9 && mode == 2) DSX_LV(K, 9, __VA_ARGS__);                      \
-  else if (c->variant == 10 && mode == 2) DSX_LV(K, 10, __VA_ARGS__);                    \
-  else
-#else
-#define DSX_ABLATE(K, ...)
-#define DSX_ABLATEL(K, ...)
-#endif
-#define DSX_LAUNCH(BR, NB, WV, SUB, PF)                                                    \
-  do {                                                                                     \
-    DSX_ABLATE(scan_kernel, BR, NB, WV, SUB, PF)                                           \
-    if (mode == 2)                                                                         \
-      hipLaunchKernelGGL((scan_kernel<2, 0, BR, NB, WV, SUB, PF>), g, b, 0, ss, sa); \
-    else if (mode == 1)                                                                    \
-      hipLaunchKernelGGL((scan_kernel<1, 0, BR, NB, WV, SUB, PF>), g, b, 0, ss, sa); \
-    else                                                                                   \
-      hipLaunchKernelGGL((scan_kernel<0, 0, BR, NB, WV, SUB, PF>), g, b, 0, ss, sa); \
-  } while (0)
-#if DSX_DIAG
-#define DSX_TRACE_VARIANTS(WV, SUB, D)                                                    \
-  if (c->variant == 5) DSX_LV(scanl_kernel, 5, WV, SUB, D);                               \
-  else if (c->variant == 6 && mode == 2) DSX_LV(scanl_kernel, 6, WV, SUB, D);             \
-  else
-#else
-#define DSX_TRACE_VARIANTS(WV, SUB, D)
-#endif
-#define DSX_LAUNCHL(WV, SUB, D, FU, TW)                                                   \
-  do {                                                                                    \
-    if (mode == 2)                                                                        \
-      hipLaunchKernelGGL((scanl_kernel<2, 0, WV, SUB, D, FU, TW>), g, b, 0, ss, sa);      \
-    else if (mode == 1)                                                                   \
-      hipLaunchKernelGGL((scanl_kernel<1, 0, WV, SUB, D, FU, TW>), g, b, 0, ss, sa);      \
-    else                                                                                  \
-      hipLaunchKernelGGL((scanl_kernel<0, 0, WV, SUB, D, FU, TW>), g, b, 0, ss, sa);      \
-  } while (0)
-#if DSX_DIAG
-    if (line && cc.behind) {
-      DSX_LAUNCHL(8, 8, 1, true, false);
-    } else
-#endif
-    if (line) {
-      DSX_ABLATEL(scanl_kernel, 8, 8, 1)
-      DSX_TRACE_VARIANTS(8, 8, 1)
-      if (c->scan_rotf && mode == 2) {  // the rotating frame (MODE 2 only)
-        if (sa.lane_bytes2)
-          hipLaunchKernelGGL((scanl_kernel<2, 0, 8, 8, 1, false, true, true>), g, b, 0, ss, sa);
-        else
-          hipLaunchKernelGGL((scanl_kernel<2, 0, 8, 8, 1, false, false, true>), g, b, 0, ss, sa);
-      } else
-      if (sa.lane_bytes2) DSX_LAUNCHL(8, 8, 1, false, true);  // two region sizes
-      else DSX_LAUNCHL(8, 8, 1, false, false);
-    } else {
-#if DSX_DIAG
-      switch (c->scan_cfg) {
-        case 1: DSX_LAUNCH(1, 2, 12, 4, false); break;
-        case 2: DSX_LAUNCH(1, 2, 16, 4, false); break;
-        case 3: DSX_LAUNCH(2, 1, 12, 8, false); break;
-        case 4: DSX_LAUNCH(2, 1, 8, 8, false); break;
-        case 5: DSX_LAUNCH(2, 1, 16, 4, false); break;
-        default:
-          if (c->prefetch_batches > 0) DSX_LAUNCH(2, 2, 8, 8, true);
-          else DSX_LAUNCH(2, 2, 8, 8, false);
-      }
-#else
-      DSX_LAUNCH(2, 2, 8, 8, false);
-#endif
-    }
-#undef DSX_LAUNCH
-#undef DSX_LAUNCHL
-#undef DSX_ABLATE
-#undef DSX_ABLATEL
-#ifdef DSX_LV
-#undef DSX_LV
-#endif
-#undef DSX_TRACE_VARIANTS
-    HIPCHK(c, hipGetLastError());
-  }
-  if (c->timing) HIPCHK(c, hipEventRecord(c->pev[3 * pi + 1], ss));
-  if (split) {  // the stitch (ctx stream) after the scan (scan stream)
-    HIPCHK(c, hipEventRecord(c->ev_scan[par], ss));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_scan[par], 0));
-  }
-  PieceCands pc{};
-  pc.P = c->last_grid_P;  // region r covers (P' + base(r), P' + base(r) + bytes(r)]
-  pc.RB = region_bytes;
-  pc.RB2 = c->last_region_bytes2;
-  pc.nbig = c->last_nbig;
-  pc.nregions = (uint32_t)nregions;
-  pc.region_cap = rcap;
-  pc.region_cnt = rcnt;
-  pc.region_list = rlist;
-  pc.overflow = sa.overflow;
-  if (kp) {
-    kp->pc = pc;
-    kp->P = P;
-    kp->len = len;
-  }
-#if DSX_DIAG
-  if (cc.behind) {
-    // the call two back finished in this scan, the last one walked in it;
-    // this one waits for the next scan (or flush_behind)
-    me.w.pc = pc;
-    me.f.overflow = sa.overflow;
-    me.f.seq = seq;
-    me.seq = seq;
-    std::deque<dsx_ctx::Behind> next;
-    for (auto& b : c->behind)
-      if (!b.walked) {
-        b.walked = true;
-        next.push_back(b);
-      }
-    next.push_back(me);
-    c->behind.swap(next);
-    c->init_pending = false;
-    c->last_finish = false;
-    if (c->timing) HIPCHK(c, hipEventRecord(c->pev[3 * pi + 2], c->stream));
-    c->stats.pieces++;
-    return DSX_OK;
-  }
-#endif
-  int rc = launch_stitch(c, cc, pc, P, len, is_last, seq, line && c->scan_trace);
-  if (rc) return rc;
-  if (split) HIPCHK(c, hipEventRecord(c->ev_stitch[par], c->stream));
-  if (c->timing) HIPCHK(c, hipEventRecord(c->pev[3 * pi + 2], c->stream));
-  c->stats.pieces++;
-  return DSX_OK;
-}
-
-// The piece's state into the pinned host slot after its stitch (the host
-// polls it for queued calls, reads it after a sync otherwise).
-static int launch_publish(dsx_ctx* c, const StitchArgs& ta) {
-  c->last_finish = ta.host_state != nullptr;
-  if (!ta.host_state) return DSX_OK;
-  if (c->defer_publish) {  // a queued call: the next scan publishes it
-    c->pub_host = ta.host_state;
-    c->pub_seq = ta.seq;
-    return DSX_OK;
-  }
-  hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, c->stream, ta);
-  HIPCHK(c, hipGetLastError());
-  return DSX_OK;
-}
-
-int flush_publish(dsx_ctx* c) {
-  if (!c->pub_host) return DSX_OK;
-  StitchArgs ta{};
-  ta.state = c->state.p;
-  ta.host_state = c->pub_host;
-  ta.seq = c->pub_seq;
-  c->pub_host = nullptr;
-  HIPCHK(c, hipSetDevice(c->device));
-  hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, c->stream, ta);
-  HIPCHK(c, hipGetLastError());
-  return DSX_OK;
-}
-
-// walk -> fixup -> gather for one piece whose candidates are in pc.
-int launch_stitch(dsx_ctx* c, const CallCfg& cc, const PieceCands& pc, uint64_t P, uint64_t len,
-                  bool is_last, uint64_t seq, bool trace) {
-  const dsx_params_t* p = cc.p;
-  const uint64_t region_bytes = pc.RB;
-  StitchArgs ta{};
-  ta.chain.min = p->min;
-  ta.chain.max = p->max;
-  ta.chain.L = cc.L;
-  ta.chain.PE = P + len;
-  ta.chain.is_last = is_last ? 1u : 0u;
-  ta.pc = pc;
-  // the carried cut lies in (P - max, P] (its successor needed bytes >= P)
-  const uint64_t anchor = (P > cc.origin + p->max) ? P - p->max : cc.origin;
-  const uint64_t end = is_last ? cc.L : P + len;
-  const uint64_t seg = stitch_seg(c, p, end > anchor ? end - anchor : 1);
-  const uint64_t nseg = end > anchor ? (end - anchor + seg - 1) / seg : 1;
-  ta.anchor = anchor;
-  ta.seg = seg;
-  ta.nseg = (uint32_t)nseg;
-  const double exp_per_seg = (double)seg / (double)p->discriminator + 8.0;
-  // segments per walk workgroup: about two workgroups per CU (the walks are
-  // latency-bound), within the LDS candidate and region budgets
-  uint64_t spg = std::max<uint64_t>(2, nseg / ((uint64_t)c->walk_wgs * (uint64_t)c->ncu));
-  // split streams: the walk runs beside the next piece's scan on the CUs the
-  // scan leaves free, two 1024-thread workgroups per CU (LDS: ~69 KiB each)
-  const bool wide = c->scan_stream != c->stream;
-  if (wide)
-    spg = std::max<uint64_t>(spg, (nseg + 2ull * c->stitch_cus - 1) / (2ull * c->stitch_cus));
-  spg = std::min<uint64_t>(spg, (uint64_t)((double)kWalkLdsCap / (2.0 * exp_per_seg)) - 1);
-  // (the smaller region size bounds the regions a workgroup's span covers:
-  // two region sizes put the short tail regions at the piece's end)
-  const uint64_t rb_min = pc.RB2 ? std::min<uint64_t>(region_bytes, pc.RB2) : region_bytes;
-  const uint64_t max_spg_reg = rb_min ? (4000ull * rb_min) / seg : kMaxSpg;
-  spg = std::min<uint64_t>(spg, max_spg_reg > 2 ? max_spg_reg - 2 : 1);
-  spg = std::max<uint64_t>(1, std::min<uint64_t>(spg, kMaxSpg));
-  ta.spg = (uint32_t)spg;
-  ta.lds_cap = kWalkLdsCap;
-  ta.scap = (uint32_t)(seg / p->min + 3);
-  HIPCHK(c, grow(c, c->seg_info, nseg));
-  HIPCHK(c, grow(c, c->stage, nseg * ta.scap));
-  HIPCHK(c, grow(c, c->rep, nseg * ta.scap));
-  HIPCHK(c, grow(c, c->rep_cnt, nseg));
-  HIPCHK(c, grow(c, c->rep_from, nseg));
-  HIPCHK(c, grow(c, c->flag_list, nseg));
-  HIPCHK(c, grow(c, c->out_off, nseg));
-  ta.seg_info = c->seg_info.p;
-  ta.stage = c->stage.p;
-  ta.rep = c->rep.p;
-  ta.rep_cnt = c->rep_cnt.p;
-  ta.rep_from = c->rep_from.p;
-  ta.flag_list = c->flag_list.p;
-  ta.out_off = c->out_off.p;
-  ta.out = cc.d_out;
-  ta.out_cap = cc.out_cap;
-  ta.state = c->state.p;
-  ta.host_state = c->h_cur;
-  ta.seq = seq;
-  ta.init = c->init_pending ? 1u : 0u;  // the call's first piece: walk_kernel resets the state
-  ta.init_carry = c->init_carry;
-  c->init_pending = false;
-  c->last_finish = false;
-  const uint32_t walk_grid = (uint32_t)((nseg + spg - 1) / spg);
-  if (trace && walk_grid <= 65536) {
-    ta.trace = c->trace.p + c->trace_base + kScanTraceWords * c->trace_n;
-    c->trace_walk_n = walk_grid;
-  }
-  const size_t walk_lds = (size_t)kWalkLdsCap * 4 + (kMaxSpg + 1) * 8;
-  if (wide)
-    hipLaunchKernelGGL(walk_kernel<1024>, dim3(walk_grid), dim3(1024), walk_lds, c->stream, ta);
-  else if (c->walk_nt == 576 && spg == 8)  // (the 8 GiB pieces: 8 segments + the redundant one, a wave each)
-    hipLaunchKernelGGL(walk_kernel<576>, dim3(walk_grid), dim3(576), walk_lds, c->stream, ta);
-  else
-    hipLaunchKernelGGL(walk_kernel<256>, dim3(walk_grid), dim3(256), walk_lds, c->stream, ta);
-  HIPCHK(c, hipGetLastError());
-  if (c->finish && nseg <= 2048) {  // fixup + gather over nseg/16 workgroups
-    const dim3 fg((uint32_t)((nseg + 15) / 16));
-    if (nseg <= 256) hipLaunchKernelGGL(finish_kernel<1>, fg, dim3(256), 0, c->stream, ta);
-    else if (nseg <= 512) hipLaunchKernelGGL(finish_kernel<2>, fg, dim3(256), 0, c->stream, ta);
-    else if (nseg <= 1024) hipLaunchKernelGGL(finish_kernel<4>, fg, dim3(256), 0, c->stream, ta);
-    else hipLaunchKernelGGL(finish_kernel<8>, fg, dim3(256), 0, c->stream, ta);
-    HIPCHK(c, hipGetLastError());
-    return launch_publish(c, ta);
-  }
-  if (c->fixup_fast && nseg <= 9 * 1024) {
-    if (nseg <= 1024) hipLaunchKernelGGL(fixup_fast_kernel<1>, dim3(1), dim3(1024), 0, c->stream, ta);
-    else if (nseg <= 2048) hipLaunchKernelGGL(fixup_fast_kernel<2>, dim3(1), dim3(1024), 0, c->stream, ta);
-    else if (nseg <= 4096) hipLaunchKernelGGL(fixup_fast_kernel<4>, dim3(1), dim3(1024), 0, c->stream, ta);
-    else if (nseg <= 5120) hipLaunchKernelGGL(fixup_fast_kernel<5>, dim3(1), dim3(1024), 0, c->stream, ta);
-    else if (nseg <= 8192) hipLaunchKernelGGL(fixup_fast_kernel<8>, dim3(1), dim3(1024), 0, c->stream, ta);
-    else hipLaunchKernelGGL(fixup_fast_kernel<9>, dim3(1), dim3(1024), 0, c->stream, ta);
-  } else {
-    hipLaunchKernelGGL(fixup_kernel, dim3(1), dim3(1024), 0, c->stream, ta);
-  }
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)nseg), dim3(256), 0, c->stream, ta);
-  HIPCHK(c, hipGetLastError());
-  return launch_publish(c, ta);
-}
-
-// Runs a whole device-resident blob [origin.., origin+len) through the engine.
-static int run_device(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, CallCfg cc) {
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc = reset_state(c, cc.origin);
-  if (rc) return rc;
-  const uint64_t piece = cc.dense ? kDensePiece : kPieceMax;
-  for (uint64_t off = 0; off < len; off += piece) {
-    if (c->cancel.load()) return DSX_E_INTERRUPTED;
-    const uint64_t n = std::min(piece, len - off);
-    rc = enqueue_piece(c, cc, d_blob + off, off + cc.halo0, cc.origin + off, n, off + n == len);
-    if (rc) return rc;
-  }
-  return DSX_OK;
-}
-
-int ensure_attr_walk(dsx_ctx* c) {
-  static bool done = false;
-  if (!done) {
-    HIPCHK(c, hipFuncSetAttribute((const void*)walk_kernel<256>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(kWalkLdsCap * 4 + (kMaxSpg + 1) * 8)));
-    HIPCHK(c, hipFuncSetAttribute((const void*)walk_kernel<576>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(kWalkLdsCap * 4 + (kMaxSpg + 1) * 8)));
-    HIPCHK(c, hipFuncSetAttribute((const void*)walk_kernel<1024>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(kWalkLdsCap * 4 + (kMaxSpg + 1) * 8)));
-    done = true;
-  }
-  return DSX_OK;
-}
-
-int flush_behind(dsx_ctx* c) {
-  const int rc = flush_tasks(c);
-  return rc ? rc : flush_publish(c);
-}
-
-int flush_tasks(dsx_ctx* c) {
-  if (c->behind.empty()) return DSX_OK;
-#if DSX_DIAG
-  HIPCHK(c, hipSetDevice(c->device));
-  // round 1: the walked call's finish and the other's walk (independent);
-  // round 2: the latter's finish
-  while (!c->behind.empty()) {
-    TaskArgs tb{};
-    tb.farrive = c->overflow.p + kArriveWord + 1;
-    for (const auto& b : c->behind) {
-      if (!b.walked) {
-        tb.w = b.w;
-        tb.nw = b.nw;
-        tb.wseg = b.wseg;
-      } else {
-        tb.f = b.f;
-        tb.nf = b.nf;
-        tb.fseg = b.fseg;
-      }
-    }
-    const uint32_t n = tb.nw + tb.nf;
-    if (n) {
-      hipLaunchKernelGGL(stitch_task_kernel, dim3((n + 3) / 4), dim3(256), 0, c->stream, tb);
-      HIPCHK(c, hipGetLastError());
-    }
-    std::deque<dsx_ctx::Behind> next;
-    for (auto& b : c->behind)
-      if (!b.walked) {
-        b.walked = true;
-        next.push_back(b);
-      }
-    c->behind.swap(next);
-  }
-#endif
-  return DSX_OK;
-}
-
 // A queued cut_device call that can be stitched behind later scans: one
 // line-aligned piece from 0, a candidate density the walk tasks' LDS holds.
 static bool behind_ok(dsx_ctx* c, const void* d_blob, uint64_t len, const dsx_params_t* p) {
@@ -1151,6 +442,25 @@ static bool behind_ok(dsx_ctx* c, const void* d_blob, uint64_t len, const dsx_pa
   return 4.0 * exp_per_seg <= (double)kTaskCand;  // wseg >= 1 with room to spare
 }
 
+// A collected call's stats: its chain state, and the scan and stitch times
+// summed over its pieces' events {before scan, after scan, after gather}.
+static void fill_stats(dsx_ctx* c, const HostState& s, const std::vector<hipEvent_t>& ev,
+                       uint32_t npiece) {
+  c->stats.chunks = s.total;
+  c->stats.repaired_segments = s.repaired;
+  c->stats.chunks_discarded = s.discarded;
+  float scan = 0, stitch = 0;
+  for (uint32_t i = 0; i < npiece; ++i) {
+    float a = 0, b = 0;
+    (void)hipEventElapsedTime(&a, ev[3 * i], ev[3 * i + 1]);
+    (void)hipEventElapsedTime(&b, ev[3 * i + 1], ev[3 * i + 2]);
+    scan += a;
+    stitch += b;
+  }
+  c->stats.scan_ms = scan;
+  c->stats.stitch_ms = stitch;
+}
+
 static int finish_call(dsx_ctx* c, uint64_t* n_out, uint64_t cap, bool* dense_retry) {
   HostState s;
   int rc = read_state(c, &s);
@@ -1160,19 +470,7 @@ static int finish_call(dsx_ctx* c, uint64_t* n_out, uint64_t cap, bool* dense_re
     *dense_retry = true;
     return DSX_OK;
   }
-  c->stats.chunks = s.total;
-  c->stats.repaired_segments = s.repaired;
-  c->stats.chunks_discarded = s.discarded;
-  float scan = 0, stitch = 0;
-  for (uint32_t i = 0; i < c->npiece_call; ++i) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, c->pev[3 * i], c->pev[3 * i + 1]);
-    (void)hipEventElapsedTime(&b, c->pev[3 * i + 1], c->pev[3 * i + 2]);
-    scan += a;
-    stitch += b;
-  }
-  c->stats.scan_ms = scan;
-  c->stats.stitch_ms = stitch;
+  fill_stats(c, s, c->pev, c->npiece_call);
   *n_out = s.total;
   if ((s.err & kErrCapacity) || s.total > cap) return DSX_E_CAPACITY;
   return DSX_OK;
@@ -1185,9 +483,6 @@ extern "C" int dsx_sync(dsx_ctx_t* c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return DSX_OK;
 }
-
-extern "C" int dsx_cut_device(dsx_ctx_t* c, const void* d_blob, uint64_t len, const dsx_params_t* p,
-                              uint64_t* out_ends, uint64_t cap, uint64_t* n_out, uint32_t flags);
 
 extern "C" int dsx_result(dsx_ctx_t* c, uint64_t* n_out) {
   if (!c || !n_out) return DSX_E_INVAL;
@@ -1236,19 +531,8 @@ extern "C" int dsx_result(dsx_ctx_t* c, uint64_t* n_out) {
     dsx_params_t p = q.p;
     return dsx_cut_device(c, q.d_blob, q.len, &p, q.out, q.cap, n_out, DSX_OUT_DEVICE);
   }
-  c->stats.chunks = s.total;
-  c->stats.repaired_segments = s.repaired;
-  c->stats.chunks_discarded = s.discarded;
-  float scan = 0, stitch = 0;  // untimed queued calls record no events
-  for (uint32_t i = 0; i < q.npiece; ++i) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, c->q_pev[q.slot][3 * i], c->q_pev[q.slot][3 * i + 1]);
-    (void)hipEventElapsedTime(&b, c->q_pev[q.slot][3 * i + 1], c->q_pev[q.slot][3 * i + 2]);
-    scan += a;
-    stitch += b;
-  }
-  c->stats.scan_ms = scan;
-  c->stats.stitch_ms = q.behind ? 0.0f : stitch;  // (inside later scans)
+  fill_stats(c, s, c->q_pev[q.slot], q.npiece);  // (untimed queued calls record no events)
+  if (q.behind) c->stats.stitch_ms = 0.0f;       // (inside later scans)
   *n_out = s.total;
   if ((s.err & kErrCapacity) || s.total > q.cap) return DSX_E_CAPACITY;
   return DSX_OK;
@@ -1554,9 +838,6 @@ extern "C" int dsx_selftest_boundary(dsx_ctx_t* c, const dsx_params_t* p, int mo
 // --------------------------------------------------------------------------
 // multi-GPU shards (split-and-align across ranks, make.go:22-163 / 277-327)
 // --------------------------------------------------------------------------
-// Chunks the shard from the cut `entry` (shard_start: speculative, make.go's
-// worker at span*i; or the true entry cut on a re-walk), builds the seam
-// record in c->d_seam, leaves the shard's cuts in c->out and waits.
 static void release_kept(dsx_ctx* c) {
   for (auto& k : c->sh.kept) {
     k.cnt.release();
@@ -1620,20 +901,12 @@ static int shard_run(dsx_ctx* c, uint64_t entry, uint32_t rec_flags, bool rewalk
       const uint64_t piece = cc.dense ? kDensePiece : kPieceMax;
       for (uint64_t off = 0; off < sh.len; off += piece) {
         const uint64_t n = std::min(piece, sh.len - off);
+        PieceCands pc{};
         rc = enqueue_piece(c, cc, sh.d + off, off + cc.halo0, sh.start + off, n,
-                           is_last && off + n == sh.len);
+                           is_last && off + n == sh.len, &pc);
         if (rc) return rc;
         if (off == 0) {
           // the window candidates come from the first piece's region lists
-          PieceCands pc{};
-          pc.P = c->last_grid_P;
-          pc.RB = c->last_region_bytes;
-          pc.RB2 = c->last_region_bytes2;
-          pc.nbig = c->last_nbig;
-          pc.nregions = c->last_nregions;
-          pc.region_cap = c->last_region_cap;
-          pc.region_cnt = cc.keep ? sh.kept[0].cnt.p : c->last_rcnt;
-          pc.region_list = cc.keep ? sh.kept[0].list.p : c->last_rlist;
           pc.overflow = nullptr;
           hipLaunchKernelGGL(seam_cands_kernel, dim3(1), dim3(64), 0, c->stream, pc, sh.start,
                              wend0, c->d_seam.p);

@@ -1,5 +1,5 @@
 // dsx_digest.h -- chunk-ID kernel interface shared by dsx_digest.hip and the
-// host engine (dsx_api.cpp).
+// host engine (dsx_engine.cpp).
 #pragma once
 #include <stdint.h>
 

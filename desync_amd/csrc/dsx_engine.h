@@ -1,6 +1,7 @@
-// dsx_engine.h -- host engine internals shared by the C-ABI translation
-// units (dsx_api.cpp: cut lists, streaming, shards; dsx_index.cpp: file ->
-// cut list + chunk IDs).  Not part of the ABI (include/dsx.h is).
+// dsx_engine.h -- host engine internals (dsx_engine.cpp) shared by the C-ABI
+// translation units (dsx_api.cpp: cut lists, shards; dsx_stream.cpp:
+// streaming; dsx_index.cpp: file -> cut list + chunk IDs).  Not part of the
+// ABI (include/dsx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include "../../include/dsx.h"
 #include "dsx_common.h"
 #include "dsx_digest.h"
+#include "dsx_scan_geom.h"
 #include "dsx_stitch.h"
 
 namespace dsx {
@@ -62,7 +64,6 @@ constexpr uint64_t kPieceMax = 8ull << 30;       // bytes per scan launch
 constexpr uint64_t kStreamBatch = 16ull << 20;   // streaming: bytes per device batch
 constexpr uint32_t kQueueDepth = 8;              // DSX_NO_SYNC calls queued per context
 constexpr uint32_t kWalkLdsCap = 8192;           // candidates per walk workgroup (2 workgroups per CU)
-constexpr uint32_t kDenseS = 48 * 9;             // dense path lane bytes (= slot cap)
 constexpr uint64_t kDensePiece = 32ull << 20;    // dense path piece size
 
 template <class T>
@@ -149,12 +150,9 @@ struct dsx_ctx {
   uint64_t trace_n = 0, trace_walk_n = 0;
   bool trace_keep = false;            // DSX_SCAN_TRACE=2: a trace slot per piece (seq % 4)
   uint64_t trace_base = 0;            // word offset of the current piece's slot
-  uint64_t last_grid_P = 0;           // region grid origin of the last enqueued piece
 
   DevBuf<uint32_t> region_cnt, region_list, overflow, rep_cnt, rep_from, flag_list;
   DevBuf<uint32_t> region_cnt2, region_list2;  // the second region-list set (split streams)
-  const uint32_t* last_rcnt = nullptr;          // region lists of the last enqueued piece
-  const uint32_t* last_rlist = nullptr;
   DevBuf<uint32_t> lane_slot;
   DevBuf<SegInfo> seg_info;
   DevBuf<uint64_t> stage, rep, out_off, out;
@@ -169,10 +167,6 @@ struct dsx_ctx {
   HostState* h_state = nullptr;  // pinned mirror published by fixup_kernel
   uint64_t piece_seq = 0;        // global piece counter (overflow parity, freshness)
   bool init_pending = false;     // next scan initialises DevState with init_carry
-  uint64_t last_region_bytes = 0;  // geometry of the last enqueued piece's region lists
-  uint32_t last_nregions = 0, last_region_cap = 0;
-  uint32_t last_nbig = 0;           // (two region sizes: regions [last_nbig, ...) have
-  uint64_t last_region_bytes2 = 0;  //  last_region_bytes2 bytes; 0: one size)
   uint64_t init_carry = 0;
   bool last_finish = false;  // the last stitch publishes its state (the host may poll)
   // a queued call's final state is published by the next scan's block 0
@@ -376,11 +370,19 @@ struct CallCfg {
   bool behind = false;  // one queued piece from 0: stitch behind later scans
 };
 
-// engine entry points (dsx_api.cpp)
+// engine entry points (dsx_engine.cpp).  Shared across translation units, so
+// external C++ symbols: the library hides none of them, and nm -D shows them
+// mangled beside the extern "C" dsx_* names, which alone are the ABI.
+TestConsts make_tc(const dsx_params_t* p);       // the scan's boundary-test constants
+int pick_mode(const dsx_ctx* c, uint32_t d);     // the scan's boundary-test MODE for d
+uint64_t stitch_seg(const dsx_ctx* c, const dsx_params_t* p, uint64_t n);
 int reset_state(dsx_ctx* c, uint64_t carry);
 int read_state(dsx_ctx* c, HostState* out);
+// *pc_out (optional): the piece's candidate lists (shards: the seam window)
 int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo,
-                  uint64_t P, uint64_t len, bool is_last);
+                  uint64_t P, uint64_t len, bool is_last, PieceCands* pc_out = nullptr);
+// a whole device-resident blob [origin.., origin+len) through the engine
+int run_device(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, CallCfg cc);
 int ensure_attr_walk(dsx_ctx* c);
 // host threads (dsx_stream.cpp): fn(0) on the caller, fn(1..parts-1) on a
 // persistent pool; returns when all have returned

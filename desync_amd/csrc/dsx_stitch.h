@@ -1,5 +1,5 @@
 // dsx_stitch.h -- device structures shared by the stitch kernels and the host
-// engine (dsx_api.cpp).
+// engine (dsx_engine.cpp).
 #pragma once
 #include <stdint.h>
 

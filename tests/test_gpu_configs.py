@@ -7,7 +7,7 @@ uniform blob, on the device, against the CPU oracle.
 * config 4: 64 GiB of zeros: 262,144 forced max-size cuts at k*max and the
   null-chunk ID (nullchunk.go:17-23) on chunks sampled in all 8 pieces.
 * 9 GiB + 12,345 B uniform: crosses 2^32 and the 8 GiB piece boundary of
-  dsx_cut_device (kPieceMax, dsx_api.cpp), compared cut for cut.
+  dsx_cut_device (kPieceMax, dsx_engine.cpp), compared cut for cut.
 * config 5: 256 GiB as 8 range shards of 32 GiB (seed 3), the seam protocol
   (dsx_shard_local / dsx_shard_resolve) for 8 ranks simulated in one process;
   every rank's list must equal the sequential chain, which is recomputed per
@@ -171,7 +171,7 @@ def test_two_region_sizes_edges(dctx, n, params):
 @pytest.mark.parametrize("n", [4 * GiB + 3 * MiB + 123, 6 * GiB + 7])
 def test_stitch_segment_doubling(dctx, n):
     """Pieces whose 1 MiB stitch segments would number more than 4097 get 2 MiB
-    ones (dsx_api.cpp stitch_seg): 4 GiB + 3 MiB is 2050 of them (just past
+    ones (dsx_engine.cpp stitch_seg): 4 GiB + 3 MiB is 2050 of them (just past
     finish_kernel's 2048: fixup_fast_kernel<4> + gather), 6 GiB 3072; cut for
     cut against the oracle, with a zero run across a 2 MiB segment boundary."""
     import torch

@@ -426,7 +426,7 @@ def _geometry(ptr, start, remaining, lanes):
     """(S, delta) of the line scan over the piece: lanes take a second
     384-byte trip once the grid exceeds 384 B per lane; the grid's origin is
     the 128-B line below the piece's first byte.  This restates
-    enqueue_piece's choice (dsx_api.cpp) under the context's defaults: 8
+    enqueue_piece's choice (dsx_scan_geom.h) under the context's defaults: 8
     waves per workgroup (scanl_waves), one region per wave slot
     (regions_per_slot), no DSX_LANE_TARGET below 768, and every CU scanning.
     If one of those defaults changes, change `lanes` and this with it: the
