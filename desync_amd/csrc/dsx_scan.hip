@@ -773,12 +773,15 @@ DSX_SCAN_INST_ALL(2, 1, 16, 4, false)
 // ds_read_b32 into a 64-register ring that serves as incoming term at once
 // and as outgoing term 48 bytes later, and one v_alignbit_b32 per byte turns
 // the frame back in front of the unchanged boundary test.
+// The test runs once per 16 bytes: the minimum of t over a pair of 8-byte
+// subgroups, one compare and branch, one hit entry of 16 bits per pair.
 // ---------------------------------------------------------------------------
 template <int MODE, int VARIANT, int W, int SUB, int D, bool FUSE, bool TWO, bool ROTF = false>
 __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
   static_assert(!ROTF || (MODE == 2 && VARIANT == 0 && D == 1 && !FUSE),
                 "the rotating frame is built for the exact MODE 2 kernel at D = 1");
   static_assert(!ROTF || rotframe::kTableBytes == kTableBytes, "table size");
+  static_assert(kLineLaneMax + 32u <= 0xFFFFu, "a hit entry keeps its group's offset in 16 bits");
   constexpr int NC = kLine / 16;             // 16-B chunks per lane row
   constexpr int NI = kWave * kLine / 1024;   // DMA wave instructions per batch
   constexpr int STG = kWave * kLine;         // staging bytes per wave
@@ -1244,6 +1247,11 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
     static_assert(D >= 1 && D <= 15 && 48 % (D + 1) == 0, "lookup distance");
     constexpr int NL = D + 1;
     uint64_t L[NL][8];  // (unused with ROTF: the lookups land in the ring)
+    // ROTF tests 16 bytes at once, the subgroups (2j, 2j+1): the even one
+    // leaves its 8 t values and their minimum here and falls through, the odd
+    // one finishes the minimum and holds the one compare and branch.  (The
+    // lookups stay per 8-byte subgroup: the ring invariant speaks of them.)
+    [[maybe_unused]] uint32_t tlo[8], thi[8], mn16 = 0;
     auto issue_sub = [&](auto gc) __attribute__((always_inline)) {
       constexpr int g = decltype(gc)::value;
 #pragma unroll
@@ -1270,9 +1278,63 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
         constexpr int r0 = rotframe::ring_in(g * 8);
         lookups_landed_u32(ring[r0], ring[r0 + 1], ring[r0 + 2], ring[r0 + 3], ring[r0 + 4],
                         ring[r0 + 5], ring[r0 + 6], ring[r0 + 7]);
-      } else {
-        lookups_landed<8>(L[g % NL]);
+        // g ^= U_i ^ U_{i-48} (one xor3), x = rotr^s(g) (one v_alignbit,
+        // amount in the phase register), t + 1 = x * ninv
+        constexpr int i0 = g * 8;
+        uint32_t(&t)[8] = (g & 1) ? thi : tlo;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          h = __builtin_amdgcn_bitop3_b32(h, ring[rotframe::ring_in(i0 + q)],
+                                          ring[rotframe::ring_out(i0 + q)], 0x96);
+          t[q] = __builtin_amdgcn_alignbit(h, h, ph[rotframe::phase_of(i0 + q)]) * tcv.ninv;
+        }
+        if constexpr ((g & 1) == 0) mn16 = t[0];
+#pragma unroll
+        for (int q = (g & 1) ? 0 : 1; q < 8; ++q) mn16 = __builtin_elementwise_min(mn16, t[q]);
+        if constexpr ((g & 1) == 0) return;  // no compare, no branch
+        if (__builtin_expect(__ballot(mn16 < tcv.vmax1) != 0, 0)) {
+          // the rare path of the 8-byte groups below, over 16 values: one
+          // entry per 16 bytes, bit q = the cut after byte q of the pair
+          uint32_t bits = 0;
+          if (__builtin_expect(__ballot(mn16 == 0u) == 0, 1)) {
+            if (tcv.rot == 0) {
+              bits = le_bits8(tlo, qlim_v) | (le_bits8(thi, qlim_v) << 8);
+            } else {
+              uint32_t xl[8], xh[8];
+#pragma unroll
+              for (int q = 0; q < 8; ++q) {
+                xl[q] = __builtin_amdgcn_alignbit(tlo[q], tlo[q], rot_v);
+                xh[q] = __builtin_amdgcn_alignbit(thi[q], thi[q], rot_v);
+              }
+              bits = le_bits8(xl, qlim_v) | (le_bits8(xh, qlim_v) << 8);
+            }
+          } else if (tcv.rot == 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              bits |= (tlo[q] - tcv.qbias <= tcv.qmax ? 1u : 0u) << q;
+              bits |= (thi[q] - tcv.qbias <= tcv.qmax ? 1u : 0u) << (q + 8);
+            }
+          } else {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+              bits |= (__builtin_amdgcn_alignbit(tlo[q], tlo[q], tcv.rot) - tcv.qbias <= tcv.qmax ? 1u : 0u)
+                      << q;
+              bits |= (__builtin_amdgcn_alignbit(thi[q], thi[q], tcv.rot) - tcv.qbias <= tcv.qmax ? 1u : 0u)
+                      << (q + 8);
+            }
+          }
+          if (bits) {  // (the pair's offset fits the low 16 bits: at most kLineLaneMax + 32)
+            const uint32_t e = (bits << 16) | (o0 + (uint32_t)((g - 1) * 8));
+#pragma unroll
+            for (int q = 0; q < kHitRegs; ++q) ereg[q] = cnt == (uint32_t)q ? e : ereg[q];
+            if (cnt >= (uint32_t)kHitRegs && cnt - kHitRegs < a.lane_slots)
+              myslots[cnt - kHitRegs] = e;
+            ++cnt;
+          }
+        }
+        return;
       }
+      lookups_landed<8>(L[g % NL]);
       // (energy ablations, wrong results: 8 = no multiply (t = h), 9 = the 8 t
       // values OR-ed with full-rate v_bitop3 instead of the v_min3 tree, 10 =
       // 4-byte lookups, the ring takes T itself)
@@ -1283,15 +1345,6 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
       uint32_t t[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        if constexpr (ROTF) {
-          // g ^= U_i ^ U_{i-48} (one xor3), x = rotr^s(g) (one v_alignbit,
-          // amount in the phase register), t + 1 = x * ninv
-          constexpr int i0 = g * 8;
-          h = __builtin_amdgcn_bitop3_b32(h, ring[rotframe::ring_in(i0 + q)],
-                                          ring[rotframe::ring_out(i0 + q)], 0x96);
-          t[q] = __builtin_amdgcn_alignbit(h, h, ph[rotframe::phase_of(i0 + q)]) * tcv.ninv;
-          continue;
-        }
         const int rk = (g * 8 + q) % 48;
         const uint32_t outv =
             VARIANT == 7 ? __builtin_amdgcn_alignbit(ring[rk], ring[rk], 16) : ring[rk];
