@@ -17,6 +17,8 @@ mirror of the reference's Go API for that path:
     NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
     DeviceStore, ChopBlob, ChunkMissing (a chunk store in HBM)  (store.go, local.go, chop.go, errors.go)
     DeviceStore.Prune, RemoveChunk, Verify(repair=True)     (local.go, cmd/desync/prune.go)
+    NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
+    DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
@@ -33,6 +35,8 @@ from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
     Segment  # noqa: F401
 from .store import ChopBlob, DeviceStore  # noqa: F401
+from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
+    NewXChaCha20Poly1305, StoreOptions  # noqa: F401
 
 __all__ = [
     "ChunkerWindowSize", "Chunker", "ChunkerReadError", "NewChunker", "Params", "SHA256", "SHA512256", "NullChunk",
@@ -43,4 +47,6 @@ __all__ = [
     "IDSet", "Info", "dedup",
     "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
     "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing",
+    "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
+    "StoreOptions", "AuthenticationError",
 ]

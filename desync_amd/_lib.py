@@ -62,6 +62,7 @@ EXPORTS = (
     "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble", "dsx_store_create", "dsx_store_destroy",
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune",
+    "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -76,6 +77,10 @@ DSX_STORE_DEVICE = 128
 DSX_ASSEMBLE_UNALIGNED = 256
 DSX_PRUNE_REMOVE = 512
 DSX_ASSEMBLE_TILE = 65536
+DSX_AEAD_XCHACHA20_POLY1305 = 0
+DSX_AEAD_NONCE = 24
+DSX_AEAD_OVERHEAD = 40     # nonce + tag
+DSX_AEAD_TILE = 262144     # plaintext bytes one workgroup of the seal / open main pass owns
 
 
 class Params(ctypes.Structure):
@@ -316,6 +321,10 @@ def lib():
             "dsx_store_resolve": (i32, [vp, vp, vp, u64, vp, u64, P(u64), P(u64), P(u32), u32]),
             "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
             "dsx_store_prune": (i32, [vp, vp, vp, u64, u64, P(StorePruneTotals), u32]),
+            "dsx_aead_seal": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, u32]),
+            "dsx_aead_open": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64,
+                                    P(u64), u32]),
+            "dsx_selftest_poly1305": (i32, [vp, vp, vp, u64, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)

@@ -268,6 +268,7 @@ extern "C" int dsx_ctx_destroy(dsx_ctx_t* c) {
   index_release(c);
   stream_release(c);
   store_release(c);
+  aead_release(c);
   idset_release(c);
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_ring) (void)hipHostFree(c->h_ring);
@@ -359,7 +360,7 @@ static uint64_t ctx_device_bytes(const dsx_ctx* c) {
   for (const auto& k : c->sh.kept) add(k.cnt), add(k.list);
   add(c->d_seam), add(c->d_all), add(c->zero_word), add(c->d_ext), add(c->d_info), add(c->d_emit);
   add(c->stamp_ring), add(c->idx_win[0]), add(c->idx_win[1]), add(c->idx_snap);
-  return b + idset_device_bytes(c) + store_device_bytes(c);
+  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c);
 }
 
 extern "C" int dsx_get_stats(dsx_ctx_t* c, dsx_stats_t* out) {

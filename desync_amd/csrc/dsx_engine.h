@@ -92,6 +92,7 @@ using namespace dsx_host;
 
 #include "dsx_idset.h"
 #include "dsx_store.h"
+#include "dsx_aead.h"
 
 // A piece's candidate lists kept past its call (shards: the O(candidates)
 // re-walk re-runs only the stitch over them)
@@ -328,6 +329,7 @@ struct dsx_ctx {
 
   IdsetScratch idset;  // chunk-ID sets (dsx_idset.hip)
   StoreScratch store;  // chunk stores (dsx_store.hip)
+  AeadScratch aead;    // the AEAD store converter (dsx_aead.hip)
 };
 
 // Grow a device buffer; outstanding work may still use the old allocation, so

@@ -17,13 +17,18 @@ and the copy, without a host round trip per chunk) and read in place by
 dsx_assemble (:func:`desync_amd.AssembleBlob` with such a store fetches
 nothing through the host).  ``Prune`` / ``RemoveChunk`` / ``Verify(repair=True)``
 remove chunks and compact the arena where it lies (dsx_store_prune), giving
-the room back to later puts.  Its capacity is fixed when it is created.  Out
-of scope: growing, copying between stores, compression, persistence, a second
-context.
+the room back to later puts.  Its capacity is fixed when it is created.
+``Seal`` / ``PutSealed`` convert its chunks to and from the records of a store
+with ``encryption: true`` (XChaCha20-Poly1305 on the GPU, encrypt.py), and
+``WriteLocal`` / ``ReadLocal`` save and reload it in LocalStore's layout, plain
+or sealed.  Out of scope: growing, copying between stores, compression (zstd),
+AES-256-GCM, a second context.
 """
 from __future__ import annotations
 
 import ctypes
+import os
+import tempfile
 import threading
 
 import numpy as np
@@ -45,6 +50,55 @@ def _check(rc, ctx):
             raise DsxError(rc, d.decode())
         _lib.check(rc, ctx.h)
     return rc
+
+
+TMP_CHUNK_PREFIX = ".tmp-cacnk"  # local.go:18
+
+
+def chunk_file_name(base, cid, extension=""):
+    """LocalStore.nameFromID (local.go:234-239) -> (directory, file path) of the
+    chunk with the 32-byte ID ``cid`` in a store at ``base``."""
+    sid = bytes(cid).hex()
+    d = os.path.join(base, sid[0:4])
+    return d, os.path.join(d, sid) + extension
+
+
+def chunk_id_from_filename(name, extension=""):
+    """chunkIDFromFilename (types.go:44-54): the 32-byte ID a chunk file's name
+    carries, or None if the name is not an ID plus ``extension``."""
+    if extension:
+        if not name.endswith(extension):
+            return None
+        name = name[:-len(extension)]
+    if len(name) != 64:
+        return None
+    try:
+        return bytes.fromhex(name)
+    except ValueError:
+        return None
+
+
+def _local_converters(converters):
+    """The converters WriteLocal / ReadLocal can apply: none, or one AEAD layer."""
+    from .encrypt import AEADConverter, Compressor, Converters
+    conv = Converters(converters)
+    if any(isinstance(c, Compressor) for c in conv):
+        raise ValueError("a compressed store cannot be written or read: zstd is not available "
+                         "(use Uncompressed: true)")
+    if len(conv) > 1 or (conv and not isinstance(conv[0], AEADConverter)):
+        raise ValueError("converters must be empty or one AEAD converter")
+    return conv
+
+
+def _umask():
+    try:
+        with open("/proc/self/status") as f:
+            for line in f:
+                if line.startswith("Umask:"):
+                    return int(line.split()[1], 8)
+    except OSError:
+        pass
+    return 0o022
 
 
 def _blob_arg(blob):
@@ -281,6 +335,164 @@ class DeviceStore:
         if not self._prune([cid], remove=True)["removed"]:
             raise ChunkMissing(cid)
 
+    # ---- storage converters and persistence (encrypt.go, local.go) -------------------------
+    def _entry_end(self, e):
+        """The arena end of entry e (0 for e < 0)."""
+        if e < 0:
+            return 0
+        end = np.empty(1, dtype=np.uint64)
+        _check(lib().dsx_store_entries(self.ctx.h, self.h, int(e), 1, None, end.ctypes.data, 0), self.ctx)
+        return int(end[0])
+
+    def Seal(self, converter, first=0, n=None, nonces=None):
+        """Seals the entries [first, first + n) where they lie in the arena, with
+        the store's device ends (dsx_aead_seal, DSX_ENDS_DEVICE): what a store with
+        ``encryption: true`` writes for them.  ``nonces``: n * 24 bytes, or None
+        for fresh random ones (as the reference draws one per chunk).  Returns
+        (the record buffer, a device tensor of uint8; the record ends as
+        np.uint64): record i is ``buffer[ends[i-1]:ends[i]]``."""
+        import torch
+        from .encrypt import AEADConverter, aead_seal
+        if not isinstance(converter, AEADConverter):
+            raise TypeError("Seal takes an AEAD converter (NewXChaCha20Poly1305)")
+        with self._lock:
+            chunks = self.counts()["chunks"]
+            n = chunks - first if n is None else int(n)
+            if first < 0 or n < 0 or first + n > chunks:
+                raise ValueError(f"entries [{first}, {first + n}) of {chunks}")
+            dev = f"cuda:{self.ctx.device}"
+            if not n:
+                return torch.empty(0, dtype=torch.uint8, device=dev), np.empty(0, dtype=np.uint64)
+            start, end = self._entry_end(first - 1), self._entry_end(first + n - 1)
+            d_ends = torch.empty(n, dtype=torch.int64, device=dev)
+            _check(lib().dsx_store_entries(self.ctx.h, self.h, int(first), n, None,
+                                           ctypes.c_void_p(d_ends.data_ptr()), _lib.DSX_OUT_DEVICE), self.ctx)
+            cap = end - start + _lib.DSX_AEAD_OVERHEAD * n
+            out = torch.empty(cap, dtype=torch.uint8, device=dev)
+            base, used = self.arena()
+            _, rec_ends = aead_seal(converter.key, base, used, d_ends.data_ptr(), start, n, nonces,
+                                    ctx=self.ctx, out=(out.data_ptr(), cap))
+            return out, rec_ends
+
+    def PutSealed(self, records, rec_ends, ids, converter, verify=True):
+        """Opens the records ``records[rec_ends[i-1]:rec_ends[i]]`` (a device tensor
+        or a ``(pointer, length)`` pair; what :meth:`Seal` returns) into a scratch
+        blob and puts the plaintexts under ``ids``.  A record that fails
+        authentication raises :class:`AuthenticationError` naming the entries
+        (``.entries``) before anything is put; with ``verify`` the plaintexts are
+        re-hashed and compared with ``ids`` first (``ChunkInvalid``).  The store is
+        unchanged on any failure.  Returns the put totals."""
+        from .encrypt import ERR_OPEN, AEADConverter, AuthenticationError, aead_open
+        from .make import chunk_ids
+        if not isinstance(converter, AEADConverter):
+            raise TypeError("PutSealed takes an AEAD converter (NewXChaCha20Poly1305)")
+        ptr, length, _keep = _blob_arg(records)
+        ids = _host_ids(ids)
+        rec_ends = np.ascontiguousarray(rec_ends, dtype=np.uint64)
+        if len(ids) != rec_ends.size:
+            raise ValueError(f"{len(ids)} IDs but {rec_ends.size} record ends")
+        with self._lock:
+            plain, ends, bad = aead_open(converter.key, ptr, length, rec_ends, 0, ctx=self.ctx)
+            if bad:
+                shown = ", ".join(str(b) for b in bad[:8]) + (", ..." if len(bad) > 8 else "")
+                raise AuthenticationError(f"{ERR_OPEN}: {len(bad)} of {rec_ends.size} records "
+                                          f"(entries {shown})", bad)
+            total = int(ends[-1]) if ends.size else 0
+            if verify and ends.size:
+                got = chunk_ids(plain.data_ptr(), total, ends, 0, ctx=self.ctx,
+                                algo=_digest_code(digest.Digest.Algorithm()))
+                got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
+                wrong = np.flatnonzero(np.any(got != ids, axis=1))
+                if wrong.size:
+                    i = int(wrong[0])
+                    raise ChunkInvalid(ids[i].tobytes(), got[i].tobytes())
+            return self.put((plain.data_ptr(), total), ids, ends, 0)
+
+    def WriteLocal(self, base, converters=()):
+        """Writes every entry as a chunk file of a LocalStore at ``base``
+        (local.go:78-98, :234-239): ``<base>/<hex[0:4]>/<hex><extension>``, through
+        a temporary file and a rename, directories 0755 and files 0644 (before
+        the umask).  ``converters`` is empty -- plain chunks, the
+        ``Uncompressed: true`` store -- or one AEAD converter, whose records are
+        made on the GPU in one call (:meth:`Seal`).  A :class:`Compressor` is
+        refused: zstd is not available.  Returns the number of files written."""
+        from .encrypt import _download
+        conv = _local_converters(converters)
+        ext = conv.storageExtension()
+        with self._lock:
+            ids, ends = self.entries()
+            if conv:
+                buf, ends = self.Seal(conv[0])
+                data = _download(self.ctx, buf.data_ptr(), int(ends[-1]) if ends.size else 0)
+            else:
+                ptr, used = self.arena()
+                data = _download(self.ctx, ptr, used)
+        prev = 0
+        for cid, end in zip(ids, ends):
+            d, p = chunk_file_name(base, cid.tobytes(), ext)
+            os.makedirs(d, mode=0o755, exist_ok=True)
+            fd, tmp = tempfile.mkstemp(prefix=TMP_CHUNK_PREFIX, dir=d)
+            try:
+                with os.fdopen(fd, "wb") as f:
+                    f.write(data[prev:int(end)].tobytes())
+                os.chmod(tmp, 0o644 & ~_umask())
+                os.rename(tmp, p)
+            except BaseException:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+                raise
+            prev = int(end)
+        return len(ids)
+
+    def ReadLocal(self, base, converters=(), ids=None, verify=True):
+        """Puts the chunks of the LocalStore at ``base`` into this store: every
+        file whose name is a chunk ID plus the converters' extension (others are
+        skipped, as local.go:148-150 does: they may belong to other settings), or
+        exactly ``ids`` (:class:`ChunkMissing` for an absent one).  Sealed records
+        are opened on the GPU in one call (:meth:`PutSealed`): a record that does
+        not authenticate -- another key -- raises and leaves the store unchanged.
+        With ``verify`` the chunks are re-hashed against their file names.
+        Returns the put totals."""
+        from .encrypt import _upload
+        conv = _local_converters(converters)
+        ext = conv.storageExtension()
+        if ids is None:
+            found = []
+            for root, _dirs, files in sorted(os.walk(base)):
+                for name in sorted(files):
+                    cid = chunk_id_from_filename(name, ext)
+                    if cid is not None:
+                        found.append((cid, os.path.join(root, name)))
+        else:
+            found = []
+            for cid in _host_ids(ids):
+                cid = cid.tobytes()
+                p = chunk_file_name(base, cid, ext)[1]
+                if not os.path.exists(p):
+                    raise ChunkMissing(cid)
+                found.append((cid, p))
+        parts = []
+        for _cid, p in found:
+            with open(p, "rb") as f:
+                parts.append(f.read())
+        cids = np.frombuffer(b"".join(c for c, _ in found), dtype=np.uint8).reshape(-1, 32)
+        ends = np.cumsum([len(b) for b in parts], dtype=np.uint64) if parts else np.empty(0, np.uint64)
+        blob = b"".join(parts)
+        with self._lock:
+            dev = _upload(self.ctx, blob)
+            if conv:
+                return self.PutSealed((dev.data_ptr(), len(blob)), ends, cids, conv[0], verify=verify)
+            if verify and len(parts):
+                from .make import chunk_ids
+                got = chunk_ids(dev.data_ptr(), len(blob), ends, 0, ctx=self.ctx,
+                                algo=_digest_code(digest.Digest.Algorithm()))
+                got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
+                wrong = np.flatnonzero(np.any(got != cids, axis=1))
+                if wrong.size:
+                    i = int(wrong[0])
+                    raise ChunkInvalid(cids[i].tobytes(), got[i].tobytes())
+            return self.put((dev.data_ptr(), len(blob)), cids, ends, 0)
+
     # ---- life ------------------------------------------------------------------------
     def close(self):
         with self._lock:
@@ -333,4 +545,4 @@ def ChopBlob(index, blob, store, verify=True):
     return store.put((ptr, length), ids, ends, 0)
 
 
-__all__ = ["DeviceStore", "ChopBlob", "OFF_NONE"]
+__all__ = ["DeviceStore", "ChopBlob", "OFF_NONE", "chunk_file_name", "chunk_id_from_filename"]

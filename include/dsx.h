@@ -32,6 +32,9 @@
  *   dsx_store_prune      <- PruneStore.Prune (store.go:35-39, local.go:163-202)
  *                           and RemoveChunk (local.go:69-75), compacting the
  *                           arena in place
+ *   dsx_aead_seal/open   <- the AEAD converter of a store with encryption: true
+ *                           (encrypt.go:84-101, XChaCha20-Poly1305, the default of
+ *                           store.go:149-156), for chunks resident in HBM
  *
  * Conventions (cgo-safe): plain pointers and sizes only; no pointer passed in
  * is retained after a call returns; every function returns 0 or a negative
@@ -625,8 +628,11 @@ int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
  * the stores still alive.  Its capacity is fixed at creation and the arena is
  * never reallocated, so its address is stable for the store's life (a prune
  * moves chunks inside it).
- * Out of scope: growing a store; copying between stores; compression and encryption converters; persistence (dsx_store_entries plus
- * the arena are enough for a caller to save and reload one); use from a second
+ * Out of scope: growing a store; copying between stores; the compression
+ * converter (zstd) and the AES-256-GCM converter -- dsx_aead_seal / dsx_aead_open
+ * below are the XChaCha20-Poly1305 one; persistence inside the library
+ * (dsx_store_entries, the arena and dsx_aead_seal are what a caller saves and
+ * reloads one with: DeviceStore.WriteLocal / ReadLocal do); use from a second
  * context or GPU. */
 typedef struct dsx_store dsx_store_t;
 
@@ -759,6 +765,58 @@ typedef struct dsx_store_prune_totals {
  * dsx_store_destroy returns DSX_E_STATE. */
 int dsx_store_prune(dsx_ctx_t *ctx, dsx_store_t *store, const void *ids, uint64_t n,
                     uint64_t window, dsx_store_prune_totals_t *totals, uint32_t flags);
+
+/* ---- the AEAD store converter: seal and open chunks in HBM -------------------------
+ * What a store with `encryption: true` writes and reads (encrypt.go:84-101):
+ * every chunk sealed on its own with XChaCha20-Poly1305 under one 256-bit key,
+ * exactly Go's chacha20poly1305.NewX(key).Seal(out, nonce, in, nil) with empty
+ * additional data.  A record is nonce(24) || ciphertext || tag(16).  DESIGN.md
+ * 4.8 has the launches.  AES-256-GCM (the reference's alternative) is not built.
+ * Both calls are synchronous on the ctx stream; their scratch counts in
+ * device_bytes; the key and everything derived from it is cleared from device
+ * memory before they return.  Results are exact and the same on every run.
+ * Refused with DSX_E_INVAL and a dsx_last_error text before any device work: a
+ * NULL context, key or buffer; an algo other than DSX_AEAD_XCHACHA20_POLY1305;
+ * an unknown flag bit; n > 0xFFFFFFF0; ends that decrease, begin below start or
+ * lie beyond the buffer; a chunk of more than 2^38 - 64 bytes (ChaCha20's 32-bit
+ * block counter starts at 1); input and output that overlap.  out_cap too small:
+ * DSX_E_CAPACITY. */
+#define DSX_AEAD_XCHACHA20_POLY1305 0
+#define DSX_AEAD_NONCE 24
+#define DSX_AEAD_OVERHEAD 40   /* nonce + tag */
+#define DSX_AEAD_TILE 262144u  /* plaintext bytes one workgroup of the main pass owns */
+
+/* Seals the chunks [start, ends[0]), [ends[0], ends[1]), ... of d_src[0..src_len)
+ * (given as in dsx_store_put; ends is host memory, or device memory with
+ * DSX_ENDS_DEVICE, then copied to the host for the checks).  Record i is
+ * d_out[(ends[i-1] - start) + 40 i, (ends[i] - start) + 40 (i + 1)); out_ends[i]
+ * (host memory, may be NULL) is its end.  nonces: n * 24 host bytes, or NULL: the
+ * library draws them from getrandom(2) and uses none twice within a call (a
+ * caller that passes them answers for never repeating one under a key). */
+int dsx_aead_seal(dsx_ctx_t *ctx, int algo, const uint8_t key[32], const void *d_src,
+                  uint64_t src_len, const uint64_t *ends, uint64_t start, uint64_t n,
+                  const uint8_t *nonces, void *d_out, uint64_t out_cap, uint64_t *out_ends,
+                  uint32_t flags);
+/* Opens the records [start, rec_ends[0]), [rec_ends[0], rec_ends[1]), ... of
+ * d_in[0..in_len) (rec_ends is host memory).  Plaintext i has max(0, record size
+ * - 40) bytes; the plaintexts are packed from d_out[0] on, out_ends[i] (host
+ * memory, may be NULL) their cumulative ends.  A record of fewer than 40 bytes
+ * (under 24: the reference's "no nonce prefix found in chunk") or whose tag does
+ * not match is bad: bad[] (host memory) receives the ascending numbers of the
+ * bad records, min(cap, *n_bad) of them, *n_bad the full count, as
+ * dsx_store_verify does, and the plaintext of every bad record is zero-filled
+ * before the call returns (Go's Open releases none).  DSX_OK in both cases: the
+ * counts are the answer.  flags: none. */
+int dsx_aead_open(dsx_ctx_t *ctx, int algo, const uint8_t key[32], const void *d_in,
+                  uint64_t in_len, const uint64_t *rec_ends, uint64_t start, uint64_t n,
+                  void *d_out, uint64_t out_cap, uint64_t *out_ends, uint32_t *bad, uint64_t cap,
+                  uint64_t *n_bad, uint32_t flags);
+/* Diagnostic: the Poly1305 tag (host memory) of d_msg[0..len) under the one-time
+ * key otk = r || s, by the device functions of the main and finish passes
+ * (tiles, powers of r, the combination).  Through the AEAD r and s cannot be
+ * chosen; this reaches the edge cases of the arithmetic mod 2^130 - 5. */
+int dsx_selftest_poly1305(dsx_ctx_t *ctx, const uint8_t otk[32], const void *d_msg, uint64_t len,
+                          uint8_t tag[16]);
 
 /* ---- statistics (ChunkingStats, make.go:329-341 + scan/stitch timings) ------ */
 typedef struct dsx_stats {
