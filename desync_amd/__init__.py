@@ -19,6 +19,7 @@ mirror of the reference's Go API for that path:
     DeviceStore.Prune, RemoveChunk, Verify(repair=True)     (local.go, cmd/desync/prune.go)
     NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
     DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
+    Copy, Cache, NewCache, DeviceStore.CopyFrom, Grow       (copy.go, cache.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
@@ -35,6 +36,7 @@ from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
     Segment  # noqa: F401
 from .store import ChopBlob, DeviceStore  # noqa: F401
+from .copy import Cache, Copy, NewCache  # noqa: F401
 from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
     NewXChaCha20Poly1305, StoreOptions  # noqa: F401
 
@@ -46,7 +48,7 @@ __all__ = [
     "index_host", "ids_fd", "ids_host", "ChopFile", "ChunkInvalid", "Hash", "NewHash",
     "IDSet", "Info", "dedup",
     "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
-    "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing",
+    "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing", "Copy", "Cache", "NewCache",
     "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
     "StoreOptions", "AuthenticationError",
 ]

@@ -61,7 +61,7 @@ EXPORTS = (
     "dsx_host_sha512_256", "dsx_idset_create", "dsx_idset_destroy", "dsx_idset_count", "dsx_dedup",
     "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble", "dsx_store_create", "dsx_store_destroy",
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
-    "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune",
+    "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
     "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305",
 )
 DSX_DIGEST_SHA512_256 = 0
@@ -76,6 +76,7 @@ DSX_SRC_STORE = -2         # ... the packed store buffer
 DSX_STORE_DEVICE = 128
 DSX_ASSEMBLE_UNALIGNED = 256
 DSX_PRUNE_REMOVE = 512
+DSX_COPY_ALL = 1024
 DSX_ASSEMBLE_TILE = 65536
 DSX_AEAD_XCHACHA20_POLY1305 = 0
 DSX_AEAD_NONCE = 24
@@ -149,6 +150,14 @@ class StorePruneTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("entries", "kept", "kept_bytes", "removed", "removed_bytes", "moved", "moved_bytes",
                  "unmatched")]
+
+
+class StoreCopyTotals(ctypes.Structure):
+    """dsx_store_copy_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("total", "copied", "copied_bytes", "present", "repeats", "missing", "first_missing",
+                 "reserved")]
 
 
 class PlanSeed(ctypes.Structure):
@@ -321,6 +330,7 @@ def lib():
             "dsx_store_resolve": (i32, [vp, vp, vp, u64, vp, u64, P(u64), P(u64), P(u32), u32]),
             "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
             "dsx_store_prune": (i32, [vp, vp, vp, u64, u64, P(StorePruneTotals), u32]),
+            "dsx_store_copy": (i32, [vp, vp, vp, vp, u64, P(StoreCopyTotals), u32]),
             "dsx_aead_seal": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, u32]),
             "dsx_aead_open": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64,
                                     P(u64), u32]),

@@ -15,8 +15,8 @@ struct dsx_ctx;
 // 0xFFFFFFFF (empty) or an entry number; the table has idset_table_cap(
 // max_chunks) slots, so its load factor never exceeds 0.5.  Nothing is ever
 // reallocated: the arena's address holds for the store's life.  chunks and
-// bytes are host copies of the fill state, advanced after each accepted put and
-// set back by a prune.  broken: a prune failed between its first and its last
+// bytes are host copies of the fill state, advanced after each accepted put or
+// copy and set back by a prune.  broken: a prune failed between its first and its last
 // write to the store, which is then neither the old nor the new one; every call
 // but dsx_store_destroy refuses it (DSX_E_STATE).
 struct dsx_store {
@@ -43,12 +43,13 @@ struct StoreScratch {
   DevBuf<uint8_t> pids;               // prune: the survivors' IDs, packed ...
   DevBuf<unsigned long long> pends;   // ... and their new ends (copied over the store's after the arena moved)
   DevBuf<uint8_t> bounce;             // prune: one window of the compacted arena
+  DevBuf<uint32_t> srce;              // copy: the source store's entry number per ID
   std::vector<dsx_store*> live;       // the context's stores
 };
 
 // put: stored, stored_bytes, present, error word; prune: kept, kept_bytes,
 // UINT64_MAX - the first removed byte's offset (0: none), -, moved, moved_bytes;
-// others: [0] a count
+// copy: copied, copied_bytes, present, missing, first_missing; others: [0] a count
 constexpr int kStoreCounters = 6;
 
 uint64_t store_device_bytes(const dsx_ctx* c);  // scratch + live stores

@@ -47,10 +47,27 @@
 //   rebuild  the new IDs and ends are copied over the store's, the table is
 //            cleared and every survivor claims a slot as the append does.
 //
-// Out of scope: growing a store;
-// compression and encryption converters; persistence (dsx_store_entries plus
-// the arena are enough for a caller to save and reload one); use from a
-// second context or GPU.
+// A copy between two stores (Copy, copy.go:9-58) is the put with a second store
+// for the blob:
+//   select  the call's own table, then one lane per ID: copy[i] = first
+//           occurrence in this call, not in dst, in src (dst is asked first,
+//           copy.go:27-33); the source entry's number and its size from src's
+//           ends; the totals, the lowest position of an ID neither store holds,
+//           and {chunks, bytes} per workgroup.  DSX_COPY_ALL reads src's IDs
+//           where they lie: they are distinct and lane i's entry is i, so it
+//           builds no table and probes only dst;
+//   scan    the put's;
+//   (the host reads the totals: an ID missing from both stores, or a copy that
+//   does not fit, ends the call here, before dst is written anywhere)
+//   append  the put's, with the gather record pointing into src's arena;
+//   copy    assemble_kernel into dst.arena[used, used + copied_bytes).
+// The appended IDs again differ from each other and from all of dst's, so the
+// claim compares none.  src is only read.  A store grows by a copy of all its
+// entries into a larger one.
+//
+// Out of scope: compression and encryption converters; persistence
+// (dsx_store_entries plus the arena are enough for a caller to save and reload
+// one); use from a second context or GPU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -83,6 +100,13 @@ struct PutArgs {
   u64* tot;       // [kStoreCounters]
   AsmSeg* segs;   // [n_new], written by the append
   u64 n_new;      // the accepted total: the append's ranks stay below it
+  // a copy between stores: ends, len and blob are the source store's ends, used
+  // bytes and arena; start is unused
+  const uint8_t* src_ids;     // the source store's IDs ...
+  const uint32_t* src_slots;  // ... and its table; null with all
+  u64 src_n, src_mask, src_salt;
+  u64 all;         // DSX_COPY_ALL: ids is src_ids, ID i is entry i, no table of the call's
+  uint32_t* srce;  // [n] the source entry of ID i (written where flag[i] is set)
 };
 
 // inclusive prefix sum over the wave's lanes
@@ -135,6 +159,63 @@ __global__ __launch_bounds__(kStoreThreads) void store_select_kernel(PutArgs a) 
   }
 }
 
+// The bytes of source entry e, [*lo, *lo + size): 0 for an entry whose ends
+// are not inside the used arena (never, in a store the library filled), so
+// that no gather record points outside it.
+__device__ __forceinline__ u64 copy_extent(const PutArgs& a, uint32_t e, u64* lo) {
+  const u64 prev = e ? a.ends[e - 1] : 0, end = a.ends[e];
+  *lo = prev;
+  return prev <= end && end <= a.len ? end - prev : 0;
+}
+
+// One lane per ID of a copy between stores.  tot[4] starts at UINT64_MAX.
+__global__ __launch_bounds__(kStoreThreads) void store_copy_select_kernel(PutArgs a) {
+  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool is_new = false, present = false, missing = false;
+  u64 size = 0;
+  if (i < a.n) {
+    const Id32 me = load_id(a.ids, i);
+    if (a.all || idset_find(a.ids, a.n, a.slots, a.mask, a.salt, me) == (uint32_t)i) {
+      present = idset_find(a.st_ids, a.st_n, a.st_slots, a.st_mask, a.st_salt, me) != kEmpty;
+      if (!present) {
+        const uint32_t e = a.all ? (uint32_t)i
+                                 : idset_find(a.src_ids, a.src_n, a.src_slots, a.src_mask, a.src_salt, me);
+        missing = e == kEmpty;
+        if (!missing) {
+          u64 lo;
+          is_new = true;
+          size = copy_extent(a, e, &lo);
+          a.srce[i] = e;
+        }
+      }
+    }
+    a.flag[i] = is_new ? 1 : 0;
+  }
+  const u64 bn = __ballot(is_new), bp = __ballot(present), bm = __ballot(missing);
+  const u64 bytes = wave_sum(size);
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    if (bn) atomicAdd(&a.tot[0], (u64)__popcll(bn));
+    if (bytes) atomicAdd(&a.tot[1], bytes);
+    if (bp) atomicAdd(&a.tot[2], (u64)__popcll(bp));
+    if (bm) {
+      atomicAdd(&a.tot[3], (u64)__popcll(bm));
+      atomicMin(&a.tot[4], i + (u64)__ffsll((unsigned long long)bm) - 1);  // (lane 0's i: the wave's first)
+    }
+    w_cnt[wave] = (u64)__popcll(bn);
+    w_bytes[wave] = bytes;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    u64 cnt = 0, by = 0;
+#pragma unroll
+    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
+    a.blk[2 * (u64)blockIdx.x] = cnt;
+    a.blk[2 * (u64)blockIdx.x + 1] = by;
+  }
+}
+
 // One workgroup: the workgroups' {chunks, bytes} pairs become their exclusive
 // prefix sums, kStoreThreads pairs a pass with a carry between passes.
 __global__ __launch_bounds__(kStoreThreads) void store_scan_kernel(u64* blk, u64 nblk) {
@@ -164,7 +245,9 @@ __global__ __launch_bounds__(kStoreThreads) void store_scan_kernel(u64* blk, u64
 
 // One lane per chunk, the grid of store_select_kernel.  Runs only after the
 // host has accepted the capacity: entry numbers stay below max_chunks and the
-// table keeps an empty slot (load factor <= 0.5).
+// table keeps an empty slot (load factor <= 0.5).  COPY: the chunk is entry
+// srce[i] of the source store (PutArgs), not chunk i of the blob.
+template <bool COPY>
 __global__ __launch_bounds__(kStoreThreads) void store_append_kernel(PutArgs a) {
   __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
@@ -173,9 +256,13 @@ __global__ __launch_bounds__(kStoreThreads) void store_append_kernel(PutArgs a) 
   u64 size = 0, prev = 0;
   if (i < a.n && a.flag[i]) {
     is_new = true;
-    const u64 e = a.ends[i];
-    prev = i ? a.ends[i - 1] : a.start;
-    if (prev <= e && e <= a.len) size = e - prev;  // (select checked it: never reads past the blob)
+    if constexpr (COPY) {
+      size = copy_extent(a, a.srce[i], &prev);  // (as select sized it: never reads past the used arena)
+    } else {
+      const u64 e = a.ends[i];
+      prev = i ? a.ends[i - 1] : a.start;
+      if (prev <= e && e <= a.len) size = e - prev;  // (select checked it: never reads past the blob)
+    }
   }
   const u64 bn = __ballot(is_new);
   const u64 ib = wave_scan(size);
@@ -419,7 +506,7 @@ int stage_ids(dsx_ctx* c, const void* ids, uint64_t n, bool device, const uint8_
 uint64_t store_device_bytes(const dsx_ctx* c) {
   const StoreScratch& t = c->store;
   uint64_t b = t.flag.n + t.blk.n * 8 + t.tot.n * 8 + t.segs.n * 8 + t.offs.n * 8 + t.sizes.n * 8 +
-               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n;
+               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n + t.srce.n * 4;
   for (const dsx_store* s : t.live) b += s->ids.n + s->ends.n * 8 + s->slots.n * 4 + s->arena.n;
   return b;
 }
@@ -428,7 +515,7 @@ void store_release(dsx_ctx* c) {
   StoreScratch& t = c->store;
   t.flag.release(), t.blk.release(), t.tot.release(), t.segs.release(), t.offs.release();
   t.sizes.release(), t.idx.release(), t.vids.release();
-  t.pids.release(), t.pends.release(), t.bounce.release();
+  t.pids.release(), t.pends.release(), t.bounce.release(), t.srce.release();
   for (dsx_store* s : t.live) free_store(s);
   t.live.clear();
 }
@@ -597,7 +684,7 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
   HIPCHK(c, grow(c, w.segs, 3 * stored));
   a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
   a.n_new = stored;
-  hipLaunchKernelGGL(store_append_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+  hipLaunchKernelGGL(store_append_kernel<false>, dim3(blocks), dim3(kStoreThreads), 0, st, a);
   HIPCHK(c, hipGetLastError());
   rc = assemble_launch(c, a.segs, stored, s->arena.p, s->bytes + stored_bytes, s->bytes,
                        s->bytes + stored_bytes, false);
@@ -950,5 +1037,112 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
     totals->moved = tot[4];
     totals->moved_bytes = tot[5];
   }
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_copy(dsx_ctx_t* c, dsx_store_t* dst, const dsx_store_t* src, const void* ids,
+                              uint64_t n, dsx_store_copy_totals_t* totals, uint32_t flags) {
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_all = DSX_COPY_ALL;
+  if (!c) return DSX_E_INVAL;
+  if (!dst || !src || !totals) return invalid(c, "a store or the totals are missing");
+  DSX_FLUSH_BEHIND(c);
+  *totals = dsx_store_copy_totals_t{};
+  totals->first_missing = UINT64_MAX;
+  if ((flags & ~(f_ids | f_all)) != 0) return invalid(c, "unknown flag bit");
+  if (dst == src) return invalid(c, "the source and the destination are the same store");
+  if (!owns(c, dst) || !owns(c, src)) return invalid(c, "the store belongs to another context");
+  if (dst->broken || src->broken) return broken(c);
+  const bool all = (flags & f_all) != 0;
+  if (all && (ids || n)) return invalid(c, "copying all entries takes no IDs: ids == NULL and n == 0");
+  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n && !ids) return invalid(c, "the IDs are missing");
+  if (all) n = src->chunks;
+  totals->total = n;
+  if (n == 0) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  IdsetScratch& t = c->idset;
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+
+  const uint8_t* d_ids = src->ids.p;
+  int rc = all ? DSX_OK : stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  if (rc) return rc;
+  const uint32_t blocks = blocks_of(n);
+  const uint64_t cap = idset_table_cap(n);
+  HIPCHK(c, grow(c, w.flag, n));
+  HIPCHK(c, grow(c, w.srce, n));
+  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+
+  // ---- select, scan ------------------------------------------------------------
+  PutArgs a{};
+  a.ids = d_ids;
+  a.n = n;
+  a.all = all ? 1 : 0;
+  if (!all) {
+    HIPCHK(c, grow(c, t.slots, cap));
+    HIPCHK(c, grow(c, t.tot, kIdsetCounters));
+    a.salt = idset_next_salt();
+    rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, a.salt, t.tot.p);
+    if (rc) return rc;
+    a.slots = t.slots.p;
+    a.mask = cap - 1;
+    a.src_slots = src->slots.p;
+  }
+  a.ends = src->ends.p;
+  a.len = src->bytes;
+  a.blob = src->arena.p;
+  a.src_ids = src->ids.p;
+  a.src_n = src->chunks;
+  a.src_mask = src->cap - 1;
+  a.src_salt = src->salt;
+  a.st_ids = dst->ids.p;
+  a.st_ends = dst->ends.p;
+  a.st_slots = dst->slots.p;
+  a.st_n = dst->chunks;
+  a.st_mask = dst->cap - 1;
+  a.st_salt = dst->salt;
+  a.st_bytes = dst->bytes;
+  a.flag = w.flag.p;
+  a.srce = w.srce.p;
+  a.blk = w.blk.p;
+  a.tot = w.tot.p;
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  HIPCHK(c, hipMemsetAsync(w.tot.p + 4, 0xFF, sizeof(u64), st));  // first_missing: none
+  hipLaunchKernelGGL(store_copy_select_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
+  HIPCHK(c, hipGetLastError());
+  // ---- the one wait before dst is written anywhere -------------------------------
+  u64 tot[kStoreCounters] = {};
+  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  const uint64_t copied = tot[0], copied_bytes = tot[1];
+  totals->copied = copied;
+  totals->copied_bytes = copied_bytes;
+  totals->present = tot[2];
+  totals->missing = tot[3];
+  totals->first_missing = tot[4];
+  totals->repeats = n - copied - tot[2] - tot[3];
+  if (tot[3]) return DSX_OK;  // (the counts are the answer: nothing is copied)
+  if (copied > dst->max_chunks - dst->chunks || copied_bytes > dst->arena_bytes - dst->bytes) {
+    c->err = "the store is full: " + std::to_string(copied) + " chunks of " +
+             std::to_string(copied_bytes) + " bytes do not fit";
+    return DSX_E_CAPACITY;
+  }
+  if (!copied) return DSX_OK;
+  // ---- append, copy ------------------------------------------------------------
+  HIPCHK(c, grow(c, w.segs, 3 * copied));
+  a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
+  a.n_new = copied;
+  hipLaunchKernelGGL(store_append_kernel<true>, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+  HIPCHK(c, hipGetLastError());
+  rc = assemble_launch(c, a.segs, copied, dst->arena.p, dst->bytes + copied_bytes, dst->bytes,
+                       dst->bytes + copied_bytes, false);
+  if (rc) return rc;
+  dst->chunks += copied;  // (the launches are enqueued: dst has the chunks from here on)
+  dst->bytes += copied_bytes;
+  HIPCHK(c, hipStreamSynchronize(st));
   return DSX_OK;
 }

@@ -299,7 +299,9 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
     segments at the store's arena, and 4. reads the arena in place; a chunk the
     store does not hold raises :class:`ChunkMissing`, a stored size that differs
     from the index's ``ValueError("unexpected size for chunk <hex>")``,
-    assemble.go:75-77); 5. dsx_chunk_ids of the result against the index's
+    assemble.go:75-77; with a :class:`Cache` of two such stores the plan's store
+    chunks are first copied into its local store, one dsx_store_copy, and that
+    store is the one read); 5. dsx_chunk_ids of the result against the index's
     IDs, the read-back check of assemble.go:208-229: a mismatch raises
     :class:`ChunkInvalid`.  An empty index gives an empty tensor
     (assemble.go:142-146).
@@ -337,7 +339,13 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
     raw = sq.ids.tobytes()
     length = int(sq.ends[-1])
     out = torch.empty(length, dtype=torch.uint8, device=dev)
+    from .copy import Cache, Copy, _on_device
     from .store import DeviceStore
+    if isinstance(store, Cache) and _on_device(store.s, store.l) and store.l.ctx is ctx:
+        # a cache of two stores in HBM: one dsx_store_copy brings what the plan
+        # needs into the local store, which is then read in place
+        Copy(sq.ids[plan.store_chunks], store.s, store.l)
+        store = store.l
     if isinstance(store, DeviceStore) and store.ctx is ctx:
         # the chunks are in HBM already: point the plan's store segments at the
         # arena (dsx_store_resolve) and gather out of it in place

@@ -5,6 +5,7 @@ Reference interface:
     LocalStore with Uncompressed: true    (local.go, store.go:98-99)
     LocalStore.Verify, with repair        (local.go:103-161)
     LocalStore.RemoveChunk, Prune         (local.go:69-75, :163-202)
+    Copy                                  (copy.go:9-58)
     desync prune's merge of the indexes   (cmd/desync/prune.go:71-81)
     ChunkStorage.StoreChunk               (chunkstorage.go:44-67)
     ChopFile                              (chop.go:14-81)
@@ -17,12 +18,13 @@ and the copy, without a host round trip per chunk) and read in place by
 dsx_assemble (:func:`desync_amd.AssembleBlob` with such a store fetches
 nothing through the host).  ``Prune`` / ``RemoveChunk`` / ``Verify(repair=True)``
 remove chunks and compact the arena where it lies (dsx_store_prune), giving
-the room back to later puts.  Its capacity is fixed when it is created.
+the room back to later puts.  ``CopyFrom`` appends chunks of another store of the
+same context (dsx_store_copy; copy.py has ``Copy`` and ``Cache``), and ``Grow``
+moves the store into a new capacity with it.
 ``Seal`` / ``PutSealed`` convert its chunks to and from the records of a store
 with ``encryption: true`` (XChaCha20-Poly1305 on the GPU, encrypt.py), and
 ``WriteLocal`` / ``ReadLocal`` save and reload it in LocalStore's layout, plain
-or sealed.  Out of scope: growing, copying between stores, compression (zstd),
-AES-256-GCM, a second context.
+or sealed.  Out of scope: compression (zstd), AES-256-GCM, a second context.
 """
 from __future__ import annotations
 
@@ -146,7 +148,7 @@ class DeviceStore:
 
     def arena(self):
         """-> (device pointer of the arena, bytes in use): the store buffer of
-        dsx_assemble with DSX_STORE_DEVICE.  The pointer holds for the store's life."""
+        dsx_assemble with DSX_STORE_DEVICE.  The pointer holds until :meth:`Grow`."""
         with self._lock:
             p, used = ctypes.c_void_p(), ctypes.c_uint64()
             _lib.check(lib().dsx_store_arena(self.h, ctypes.byref(p), ctypes.byref(used)))
@@ -334,6 +336,65 @@ class DeviceStore:
             raise ValueError("a chunk ID is 32 bytes")
         if not self._prune([cid], remove=True)["removed"]:
             raise ChunkMissing(cid)
+
+    # ---- copying between stores, growing (copy.go) ------------------------------------------
+    def CopyFrom(self, src, ids=None, n=None):
+        """dsx_store_copy: appends the chunks of ``src`` (a :class:`DeviceStore`
+        of the same context) that ``ids`` names and this store does not hold, in
+        the order of their first occurrence, without a host round trip.  ``ids``
+        is as for :class:`IDSet` (host, or device memory with ``n``); ``None``
+        means every entry of ``src`` (DSX_COPY_ALL).  Returns the totals as a
+        dict: total, copied, copied_bytes, present, repeats, missing,
+        first_missing.  All or nothing: with ``missing`` > 0 nothing was copied
+        (``first_missing`` is the lowest position in ``ids`` of an ID neither
+        store holds; :func:`desync_amd.Copy` raises :class:`ChunkMissing` for
+        it), and a copy that does not fit raises DsxError (DSX_E_CAPACITY) with
+        ``.totals`` what it would have copied; the store is unchanged either way."""
+        if not isinstance(src, DeviceStore):
+            raise TypeError("CopyFrom takes a DeviceStore (desync_amd.Copy copies from any store)")
+        if ids is None:
+            iptr, n, flags, _keep = 0, 0, _lib.DSX_COPY_ALL, None
+        else:
+            iptr, n, flags, _keep = _ids_arg(ids, n)
+        tot = _lib.StoreCopyTotals()
+        first, second = sorted((self, src), key=id)  # (one lock order for every pair)
+        with first._lock, second._lock:
+            rc = lib().dsx_store_copy(self.ctx.h, self.h, src.h, ctypes.c_void_p(iptr), n,
+                                      ctypes.byref(tot), flags)
+            totals = {k: getattr(tot, k) for k, _ in _lib.StoreCopyTotals._fields_ if k != "reserved"}
+            try:
+                _check(rc, self.ctx)
+            except DsxError as e:
+                e.totals = totals
+                raise
+        return totals
+
+    def Grow(self, arena_bytes, max_chunks):
+        """Gives the store a new capacity: creates a store of ``arena_bytes``
+        and ``max_chunks``, copies every entry into it in entry order
+        (dsx_store_copy with DSX_COPY_ALL: the same entries, ends and arena
+        bytes), and destroys the old one.  If the new capacity is below the
+        current fill the copy raises DsxError (DSX_E_CAPACITY) and the store
+        stays as it was.  The arena's address changes: offsets taken before
+        (``arena``, ``locate``, a resolved plan) are stale afterwards, as after
+        a prune.  Needs the memory of both stores while it runs.  Returns the
+        copy's totals."""
+        with self._lock:
+            h = ctypes.c_void_p()
+            _check(lib().dsx_store_create(self.ctx.h, int(arena_bytes), int(max_chunks), ctypes.byref(h)),
+                   self.ctx)
+            tot = _lib.StoreCopyTotals()
+            rc = lib().dsx_store_copy(self.ctx.h, h, self.h, None, 0, ctypes.byref(tot), _lib.DSX_COPY_ALL)
+            totals = {k: getattr(tot, k) for k, _ in _lib.StoreCopyTotals._fields_ if k != "reserved"}
+            try:
+                _check(rc, self.ctx)
+            except DsxError as e:
+                lib().dsx_store_destroy(self.ctx.h, h)
+                e.totals = totals
+                raise
+            old, self.h = self.h, h
+            lib().dsx_store_destroy(self.ctx.h, old)
+        return totals
 
     # ---- storage converters and persistence (encrypt.go, local.go) -------------------------
     def _entry_end(self, e):

@@ -32,6 +32,7 @@
  *   dsx_store_prune      <- PruneStore.Prune (store.go:35-39, local.go:163-202)
  *                           and RemoveChunk (local.go:69-75), compacting the
  *                           arena in place
+ *   dsx_store_copy       <- Copy (copy.go:9-58) between two stores in HBM
  *   dsx_aead_seal/open   <- the AEAD converter of a store with encryption: true
  *                           (encrypt.go:84-101, XChaCha20-Poly1305, the default of
  *                           store.go:149-156), for chunks resident in HBM
@@ -627,9 +628,8 @@ int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
  * its memory counts in that context's device_bytes, and dsx_ctx_destroy frees
  * the stores still alive.  Its capacity is fixed at creation and the arena is
  * never reallocated, so its address is stable for the store's life (a prune
- * moves chunks inside it).
- * Out of scope: growing a store; copying between stores; the compression
- * converter (zstd) and the AES-256-GCM converter -- dsx_aead_seal / dsx_aead_open
+ * moves chunks inside it); a store grows by dsx_store_copy into a larger one.
+ * Out of scope: the compression converter (zstd) and the AES-256-GCM converter -- dsx_aead_seal / dsx_aead_open
  * below are the XChaCha20-Poly1305 one; persistence inside the library
  * (dsx_store_entries, the arena and dsx_aead_seal are what a caller saves and
  * reloads one with: DeviceStore.WriteLocal / ReadLocal do); use from a second
@@ -765,6 +765,54 @@ typedef struct dsx_store_prune_totals {
  * dsx_store_destroy returns DSX_E_STATE. */
 int dsx_store_prune(dsx_ctx_t *ctx, dsx_store_t *store, const void *ids, uint64_t n,
                     uint64_t window, dsx_store_prune_totals_t *totals, uint32_t flags);
+
+/* Copy (copy.go:9-58; desync cache, and what a Cache in front of a store does
+ * with every chunk it fetches, cache.go:24-45) between two stores of one
+ * context, and what growing a store is made of: DSX_COPY_ALL into a new store
+ * of another capacity. */
+#define DSX_COPY_ALL 1024u  /* ids == NULL, n == 0: every entry of src, in entry order */
+
+typedef struct dsx_store_copy_totals {
+    uint64_t total;          /* n (DSX_COPY_ALL: src's entry count) */
+    uint64_t copied, copied_bytes; /* distinct chunks appended to dst by this call */
+    uint64_t present;        /* first occurrences in this call that dst already held */
+    uint64_t repeats;        /* occurrences repeating an earlier ID of this call */
+    uint64_t missing;        /* first occurrences neither dst nor src holds */
+    uint64_t first_missing;  /* lowest position in ids[] of one, else UINT64_MAX */
+    uint64_t reserved;       /* 0 */
+} dsx_store_copy_totals_t;   /* 64 bytes */
+
+/* ids[] holds n 32-byte IDs (host memory, or device memory with
+ * DSX_IDS_DEVICE; duplicates allowed).  An ID is copied exactly when it is the
+ * first occurrence in this call, dst does not hold it and src does.  dst is
+ * asked first (copy.go:27-33): an ID dst holds counts as present whether or not
+ * src holds it.  New chunks are appended to dst in the order of their first
+ * occurrence in ids[], tightly packed, entry e at [ends[e-1], ends[e]);
+ * zero-length chunks take an entry of size 0.  The arena, the entry order and
+ * the totals are exact and the same on every run; total == copied + present +
+ * repeats + missing.
+ * All or nothing.  With missing > 0 the call returns DSX_OK, copies nothing and
+ * leaves dst untouched: missing and first_missing are the answer, as the counts
+ * of dsx_store_resolve are (copied and copied_bytes then count what the call
+ * would have copied of the rest).  With chunks + copied > max_chunks or bytes +
+ * copied_bytes > arena_bytes it returns DSX_E_CAPACITY, the totals say what it
+ * would have copied, and dst is unchanged.  Both are decided after the
+ * selecting launch, before any entry, slot or arena byte of dst is written.
+ * DSX_COPY_ALL: the IDs are src's own, read where they lie; into an empty dst
+ * the result has the same entries, the same ends and the same used arena bytes
+ * as src.
+ * Refused with DSX_E_INVAL (and, given a ctx, a dsx_last_error text) before any
+ * device work: a NULL ctx, dst, src or totals; dst == src; either store
+ * belonging to another context; ids == NULL with n > 0 and no DSX_COPY_ALL;
+ * DSX_COPY_ALL with ids != NULL or n != 0; n > 0xFFFFFFF0; any flag bit other
+ * than DSX_IDS_DEVICE and DSX_COPY_ALL.  A broken store on either side:
+ * DSX_E_STATE.  n == 0 without DSX_COPY_ALL: zero counts (first_missing
+ * UINT64_MAX), DSX_OK.
+ * Synchronous on the ctx stream: one host wait after the selection, one at the
+ * end.  src is only read.  No kernel reads outside src's used arena or writes
+ * outside dst's arena. */
+int dsx_store_copy(dsx_ctx_t *ctx, dsx_store_t *dst, const dsx_store_t *src,
+                   const void *ids, uint64_t n, dsx_store_copy_totals_t *totals, uint32_t flags);
 
 /* ---- the AEAD store converter: seal and open chunks in HBM -------------------------
  * What a store with `encryption: true` writes and reads (encrypt.go:84-101):
