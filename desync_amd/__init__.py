@@ -16,6 +16,7 @@ mirror of the reference's Go API for that path:
     Info, IDSet, dedup (chunk-ID sets on the GPU)           (cmd/desync/info.go, fileseed.go)
     NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
     DeviceStore, ChopBlob, ChunkMissing (a chunk store in HBM)  (store.go, local.go, chop.go, errors.go)
+    IndexFromBlobs, ChopBlobs, cut_device_many (many blobs per call)  (make.go, chop.go)
     DeviceStore.Prune, RemoveChunk, Verify(repair=True)     (local.go, cmd/desync/prune.go)
     NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
     DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
@@ -28,14 +29,14 @@ from .digest import SHA256, SHA512256, NewNullChunk, NullChunk, set_digest  # no
 from .errors import ChunkInvalid, ChunkMissing, Interrupted  # noqa: F401
 from .index import FormatIndex, Index, IndexChunk, IndexFromReader  # noqa: F401
 from .stream import Chunk, ChunkStorage, ChunkStream, MemoryStore  # noqa: F401
-from .make import ChunkingStats, IndexFromFile, VerifyError, VerifyIndex, chunk_ids, cut_device, cut_device_result, \
+from .make import ChunkingStats, IndexFromBlobs, IndexFromFile, VerifyError, cut_device_many, VerifyIndex, chunk_ids, cut_device, cut_device_result, \
     cut_fd, cut_host, file_size, ids_fd, ids_host, index_fd, index_host  # noqa: F401
 from .chop import ChopFile  # noqa: F401
 from .hash import Hash, NewHash  # noqa: F401
 from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
     Segment  # noqa: F401
-from .store import ChopBlob, DeviceStore  # noqa: F401
+from .store import ChopBlob, ChopBlobs, DeviceStore  # noqa: F401
 from .copy import Cache, Copy, NewCache  # noqa: F401
 from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
     NewXChaCha20Poly1305, StoreOptions  # noqa: F401
@@ -50,5 +51,5 @@ __all__ = [
     "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
     "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing", "Copy", "Cache", "NewCache",
     "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
-    "StoreOptions", "AuthenticationError",
+    "StoreOptions", "AuthenticationError", "IndexFromBlobs", "ChopBlobs", "cut_device_many",
 ]

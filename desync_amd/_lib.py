@@ -62,7 +62,7 @@ EXPORTS = (
     "dsx_plan_walk", "dsx_seed_plan", "dsx_assemble", "dsx_store_create", "dsx_store_destroy",
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
-    "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305",
+    "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305", "dsx_cut_device_many",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -158,6 +158,21 @@ class StoreCopyTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("total", "copied", "copied_bytes", "present", "repeats", "missing", "first_missing",
                  "reserved")]
+
+
+class ManyOpts(ctypes.Structure):
+    """dsx_many_opts_t: 0 in a field is the library's default."""
+
+    _fields_ = [("big_blob", ctypes.c_uint64), ("group_bytes", ctypes.c_uint64),
+                ("reserved", ctypes.c_uint64 * 2)]
+
+
+class ManyTotals(ctypes.Structure):
+    """dsx_many_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("blobs", "empty_blobs", "chunks", "groups", "batched_blobs", "single_blobs",
+                 "redone_blobs", "reserved")]
 
 
 class PlanSeed(ctypes.Structure):
@@ -272,6 +287,8 @@ def lib():
             "dsx_cancel": (i32, [vp]),
             "dsx_progress": (i32, [vp, P(u64)]),
             "dsx_cut_device": (i32, [vp, vp, u64, P(Params), vp, u64, P(u64), u32]),
+            "dsx_cut_device_many": (i32, [vp, vp, u64, vp, u64, P(Params), vp, u64, P(u64), vp,
+                                          P(ManyOpts), P(ManyTotals), u32]),
             "dsx_sync": (i32, [vp]),
             "dsx_result": (i32, [vp, P(u64)]),
             "dsx_cut_host": (i32, [vp, vp, u64, P(Params), vp, u64, P(u64)]),

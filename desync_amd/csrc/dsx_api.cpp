@@ -269,6 +269,7 @@ extern "C" int dsx_ctx_destroy(dsx_ctx_t* c) {
   stream_release(c);
   store_release(c);
   aead_release(c);
+  many_release(c);
   idset_release(c);
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_ring) (void)hipHostFree(c->h_ring);
@@ -360,7 +361,7 @@ static uint64_t ctx_device_bytes(const dsx_ctx* c) {
   for (const auto& k : c->sh.kept) add(k.cnt), add(k.list);
   add(c->d_seam), add(c->d_all), add(c->zero_word), add(c->d_ext), add(c->d_info), add(c->d_emit);
   add(c->stamp_ring), add(c->idx_win[0]), add(c->idx_win[1]), add(c->idx_snap);
-  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c);
+  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c) + many_device_bytes(c);
 }
 
 extern "C" int dsx_get_stats(dsx_ctx_t* c, dsx_stats_t* out) {
@@ -629,6 +630,52 @@ extern "C" int dsx_cut_device(dsx_ctx_t* c, const void* d_blob, uint64_t len, co
   }
   c->err = "dense-candidate path overflowed";
   return DSX_E_INTERNAL;
+}
+
+// Many blobs packed in one device buffer -> one cut list whose chain restarts
+// at every blob boundary (the engine: run_many, dsx_engine.cpp).  Every
+// refusal comes before HIP is touched.
+extern "C" int dsx_cut_device_many(dsx_ctx_t* c, const void* d_blob, uint64_t len,
+                                   const uint64_t* blob_ends, uint64_t nblobs,
+                                   const dsx_params_t* p, uint64_t* out_ends, uint64_t cap,
+                                   uint64_t* n_out, uint64_t* blob_first,
+                                   const dsx_many_opts_t* opts, dsx_many_totals_t* totals,
+                                   uint32_t flags) {
+  if (!c || !p || !n_out) return DSX_E_INVAL;
+  auto refuse = [&](const char* why) {
+    c->err = why;
+    return DSX_E_INVAL;
+  };
+  if ((flags & ~DSX_OUT_DEVICE) != 0) return refuse("cut_device_many: flags other than the output's place");
+  if (nblobs && !blob_ends) return refuse("cut_device_many: no blob ends");
+  if (!nblobs && len) return refuse("cut_device_many: bytes but no blob");
+  if (nblobs > 0xFFFFFFF0ull) return refuse("cut_device_many: more than 2^32 - 16 blobs");
+  if (len && !d_blob) return refuse("cut_device_many: no buffer");
+  if (cap && !out_ends) return refuse("cut_device_many: a capacity but no output");
+  if (opts) {
+    if (opts->reserved[0] || opts->reserved[1]) return refuse("cut_device_many: reserved option fields must be 0");
+    if (opts->group_bytes > kPieceMax) return refuse("cut_device_many: more than 8 GiB per scan launch");
+  }
+  for (uint64_t i = 0, prev = 0; i < nblobs; prev = blob_ends[i++])
+    if (blob_ends[i] < prev) return refuse("cut_device_many: blob ends decrease");
+  if (nblobs && blob_ends[nblobs - 1] != len) return refuse("cut_device_many: the last blob does not end the buffer");
+  if (p->min < (uint64_t)kRound || p->discriminator == 0) return refuse("cut_device_many: parameters not from dsx_params_init");
+
+  c->cancel.store(0);
+  *n_out = 0;
+  if (totals) *totals = dsx_many_totals_t{};
+  if (nblobs == 0) return DSX_OK;
+  int rc = ensure_attr_walk(c);
+  if (rc) return rc;
+  // queued calls: as a synchronous dsx_cut_device treats them
+  rc = flush_tasks(c);
+  if (rc) return rc;
+  rc = flush_publish(c);
+  if (rc) return rc;
+  const uint64_t big = opts && opts->big_blob ? opts->big_blob : many_default_big_blob(p);
+  const uint64_t group = opts && opts->group_bytes ? opts->group_bytes : kPieceMax;
+  return run_many(c, (const uint8_t*)d_blob, len, blob_ends, nblobs, p, out_ends, cap, n_out,
+                  blob_first, big, group, totals, (flags & DSX_OUT_DEVICE) != 0);
 }
 
 // --------------------------------------------------------------------------

@@ -146,7 +146,33 @@ __device__ __forceinline__ uint32_t rel_step(uint32_t s, WaveLdsSrc& src, const 
 }
 static_assert(kRelUndet > kRelClamp, "kRelUndet must exceed every relative position");
 
+// ---- shared by the walks (dsx_stitch.hip, dsx_many.hip) ----------------------
+constexpr uint32_t kWalkMaxRegions = 4096;  // regions a walk workgroup can stage
 
+// Block-wide exclusive scan of one value per thread (NT threads); returns the
+// exclusive prefix, *total gets the block sum.
+template <int NT>
+__device__ uint32_t walk_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(incl, d, 64);
+    if (lane >= (uint32_t)d) incl += t;
+  }
+  if (lane == 63) s_wave[wv] = incl;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) {
+    const uint32_t t = s_wave[i];
+    before += (i < (int)wv) ? t : 0u;
+    all += t;
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl - v;
+}
 
 __device__ __forceinline__ uint64_t seg_start(const StitchArgs& a, uint64_t s0, uint32_t k) {
   return k == 0 ? s0 : a.anchor + (uint64_t)k * a.seg;

@@ -359,11 +359,11 @@ static int trace_slot(dsx_ctx* c, bool behind, int W, uint64_t seq, hipStream_t 
   return DSX_OK;
 }
 
-// Enqueue scan + stitch for one piece [P, P+len) whose bytes are at d_piece
-// (with `halo` readable bytes before it).  *pc_out: the piece's candidate
-// lists as the stitch reads them.
-int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo,
-                  uint64_t P, uint64_t len, bool is_last, PieceCands* pc_out) {
+// Enqueue the scan of one piece [P, P+len) whose bytes are at d_piece (with
+// `halo` readable bytes before it).  so->pc: the piece's candidate lists as a
+// stitch reads them (on the ctx stream, which waits for the scan).
+int enqueue_scan(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo, uint64_t P,
+                 uint64_t len, ScanOut* so, const TaskArgs* behind_tb) {
   const dsx_params_t* p = cc.p;
   const bool split = c->scan_stream != c->stream;
   const ScanGeom g = scan_geom(geom_in(c, cc, d_piece, halo, P, len));
@@ -373,17 +373,6 @@ int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_
   KeptPiece* kp = nullptr;
   int rc = region_lists(c, cc, g, &rcnt, &rlist, &kp);
   if (rc) return rc;
-  // stitch behind: this call's jobs, and the tasks of the calls behind it
-  // that this scan carries
-#if DSX_DIAG
-  TaskArgs tb{};
-  dsx_ctx::Behind me;
-  if (cc.behind) {
-    rc = behind_jobs(c, cc, len, &me);
-    if (rc) return rc;
-    behind_tasks(c, &tb);
-  }
-#endif
   const uint64_t seq = ++c->piece_seq;
   const int par = (int)(seq & 1);
   hipStream_t ss = c->scan_stream;
@@ -426,7 +415,8 @@ int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_
     c->pub_host = nullptr;
   }
 #if DSX_DIAG
-  if (cc.behind) {
+  if (behind_tb) {
+    TaskArgs tb = *behind_tb;
     tb.counter = sa.queue + 1;  // (zeroed by the previous scan, with the queue)
     tb.farrive = sa.queue + 2;
     // the ring advances with fused calls only: the slot was last read by the
@@ -492,15 +482,47 @@ int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_
     kp->P = P;
     kp->len = len;
   }
-  if (pc_out) *pc_out = pc;
+  so->pc = pc;
+  so->seq = seq;
+  so->pi = pi;
+  so->line = line;
+  return DSX_OK;
+}
+
+// Enqueue scan + stitch for one piece [P, P+len) whose bytes are at d_piece
+// (with `halo` readable bytes before it).  *pc_out: the piece's candidate
+// lists as the stitch reads them.
+int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo,
+                  uint64_t P, uint64_t len, bool is_last, PieceCands* pc_out) {
+  const bool split = c->scan_stream != c->stream;
+  int rc;
+  ScanOut so;
+  // stitch behind: this call's jobs, and the tasks of the calls behind it
+  // that this scan carries
+#if DSX_DIAG
+  TaskArgs tb{};
+  dsx_ctx::Behind me;
+  if (cc.behind) {
+    rc = behind_jobs(c, cc, len, &me);
+    if (rc) return rc;
+    behind_tasks(c, &tb);
+  }
+  rc = enqueue_scan(c, cc, d_piece, halo, P, len, &so, cc.behind ? &tb : nullptr);
+#else
+  rc = enqueue_scan(c, cc, d_piece, halo, P, len, &so);
+#endif
+  if (rc) return rc;
+  const uint32_t pi = so.pi;
+  const int par = (int)(so.seq & 1);
+  if (pc_out) *pc_out = so.pc;
 #if DSX_DIAG
   if (cc.behind) {
     // the call two back finished in this scan, the last one walked in it;
     // this one waits for the next scan (or flush_behind)
-    me.w.pc = pc;
-    me.f.overflow = sa.overflow;
-    me.f.seq = seq;
-    me.seq = seq;
+    me.w.pc = so.pc;
+    me.f.overflow = so.pc.overflow;
+    me.f.seq = so.seq;
+    me.seq = so.seq;
     behind_rotate(c, &me);
     c->init_pending = false;
     c->last_finish = false;
@@ -509,7 +531,7 @@ int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_
     return DSX_OK;
   }
 #endif
-  rc = launch_stitch(c, cc, pc, P, len, is_last, seq, line && c->scan_trace);
+  rc = launch_stitch(c, cc, so.pc, P, len, is_last, so.seq, so.line && c->scan_trace);
   if (rc) return rc;
   if (split) HIPCHK(c, hipEventRecord(c->ev_stitch[par], c->stream));
   if (c->timing) HIPCHK(c, hipEventRecord(c->pev[3 * pi + 2], c->stream));
@@ -700,5 +722,193 @@ int flush_tasks(dsx_ctx* c) {
     behind_rotate(c);
   }
 #endif
+  return DSX_OK;
+}
+
+// --------------------------------------------------------------------------
+// many blobs in one packed buffer (dsx_cut_device_many)
+// --------------------------------------------------------------------------
+// The batched walk's positions are 32-bit offsets from a run's start, and a
+// step of max (clamped to 2^30) must stay in them: a longer blob is single.
+constexpr uint64_t kManyMaxBatched = 1ull << 30;
+constexpr uint32_t kManyRunBlobs = 4096;  // blobs per walk workgroup (16 rounds of its 4 waves)
+static_assert(sizeof(ManyRun) == sizeof(ManyRunDev), "the plan's runs are uploaded as they are");
+static_assert(kManyLdsCap == kWalkLdsCap, "the batched walk stages what walk_kernel stages");
+
+// The length whose expected candidate count (len / discriminator + 8) is half
+// of what a walk workgroup stages: longer blobs take the one-blob path.
+uint64_t many_default_big_blob(const dsx_params_t* p) {
+  return std::min<uint64_t>(kManyMaxBatched, (uint64_t)(kWalkLdsCap / 2 - 8) * p->discriminator);
+}
+
+void many_release(dsx_ctx* c) {
+  c->many.ends.release(); c->many.stage.release(); c->many.first.release();
+  c->many.res.release(); c->many.cnt.release(); c->many.runs.release();
+}
+
+uint64_t many_device_bytes(const dsx_ctx* c) {
+  const auto& m = c->many;
+  return (m.ends.n + m.stage.n + m.first.n + m.res.n) * sizeof(uint64_t) +
+         m.cnt.n * sizeof(uint32_t) + m.runs.n * sizeof(ManyRunDev);
+}
+
+// Blob i = [B0, B1) on the one-blob path (run_device, with the dense retry of
+// dsx_cut_device), its cuts into its slots of the staging list.
+static int many_single(dsx_ctx* c, const uint8_t* d_blob, const ManyBlobs& mb,
+                       const dsx_params_t* p, uint64_t i, uint64_t B0, uint64_t B1) {
+  const uint64_t slots = (B1 - B0) / p->min + 1;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    CallCfg cc{p, B1, B0, B0 + kRound, mb.stage + (B0 / p->min + i), slots, attempt == 1};
+    cc.halo0 = B0;
+    int rc = run_device(c, d_blob + B0, B1 - B0, cc);
+    if (rc) return rc;
+    HostState s;
+    rc = read_state(c, &s);
+    if (rc) return rc;
+    if (s.err & kErrDense) {
+      c->stats.dense_fallbacks++;
+      continue;
+    }
+    if ((s.err & kErrCapacity) || s.total > slots) {
+      c->err = "a blob has more cuts than its slots of the staging list";
+      return DSX_E_INTERNAL;
+    }
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(mb.cnt + i), (int)s.total, 1, c->stream));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(mb.flag + i), 0, 1, c->stream));
+    return DSX_OK;
+  }
+  c->err = "dense-candidate path overflowed";
+  return DSX_E_INTERNAL;
+}
+
+// One group: a scan launch over its bytes, then the batched walk.
+static int many_group(dsx_ctx* c, const uint8_t* d_blob, const ManyBlobs& mb, const dsx_params_t* p,
+                      const uint64_t* blob_ends, const ManyItem& it, std::vector<ManyRun>* runs) {
+  const bool split = c->scan_stream != c->stream;
+  // chain origin = the group's start; the bytes before it in the packed
+  // buffer are its halo (a group off the 128-byte grid keeps the line scan)
+  CallCfg cc{p, it.end, it.start, it.start + kRound, nullptr, 0, false};
+  c->npiece_call = 0;  // (no timing events: the groups are not pieces of a chain)
+  const bool timing = c->timing;
+  c->timing = false;
+  ScanOut so;
+  const int rc = enqueue_scan(c, cc, d_blob + it.start, it.start, it.start, it.end - it.start, &so);
+  c->timing = timing;
+  if (rc) return rc;
+  // blobs per walk workgroup: expected candidates within half of its LDS, the
+  // regions it can stage, and enough workgroups for the device
+  const PieceCands& pc = so.pc;
+  const uint64_t rb_min = pc.RB2 ? std::min<uint64_t>(pc.RB, pc.RB2) : pc.RB;
+  uint64_t span = (uint64_t)(kWalkLdsCap / 2 - 8) * p->discriminator;
+  if (rb_min) span = std::min<uint64_t>(span, 3998ull * rb_min);
+  span = std::min<uint64_t>(span, kManyMaxBatched);
+  span = std::min<uint64_t>(span, std::max<uint64_t>((it.end - it.start) / (4ull * c->ncu), 256ull << 10));
+  many_runs(blob_ends, it.b0, it.b1, span, kManyRunBlobs, runs);
+  HIPCHK(c, grow(c, c->many.runs, runs->size()));
+  HIPCHK(c, hipMemcpyAsync(c->many.runs.p, runs->data(), runs->size() * sizeof(ManyRun),
+                           hipMemcpyHostToDevice, c->stream));
+  ManyWalkArgs wa{};
+  wa.mb = mb;
+  wa.pc = pc;
+  wa.runs = c->many.runs.p;
+  wa.lds_cap = kWalkLdsCap;
+  hipLaunchKernelGGL(many_walk_kernel, dim3((uint32_t)runs->size()), dim3(kManyWalkThreads), 0,
+                     c->stream, wa);
+  HIPCHK(c, hipGetLastError());
+  if (split) HIPCHK(c, hipEventRecord(c->ev_stitch[so.seq & 1], c->stream));
+  return DSX_OK;
+}
+
+int run_many(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, const uint64_t* blob_ends,
+             uint64_t nblobs, const dsx_params_t* p, uint64_t* out_ends, uint64_t cap,
+             uint64_t* n_out, uint64_t* blob_first, uint64_t big_blob, uint64_t group_bytes,
+             dsx_many_totals_t* totals, bool dev_out) {
+  HIPCHK(c, hipSetDevice(c->device));
+  big_blob = std::min<uint64_t>(big_blob, kManyMaxBatched);
+  const std::vector<ManyItem> items = many_plan(blob_ends, nblobs, big_blob, group_bytes);
+  auto& m = c->many;
+  HIPCHK(c, grow(c, m.ends, nblobs));
+  HIPCHK(c, grow(c, m.stage, len / p->min + nblobs + 1));
+  HIPCHK(c, grow(c, m.cnt, 2 * nblobs));
+  HIPCHK(c, grow(c, m.first, nblobs + 1));
+  HIPCHK(c, grow(c, m.res, 2));
+  HIPCHK(c, hipMemcpyAsync(m.ends.p, blob_ends, nblobs * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(m.cnt.p, 0, 2 * nblobs * sizeof(uint32_t), c->stream));
+  ManyBlobs mb{};
+  mb.ends = m.ends.p;
+  mb.stage = m.stage.p;
+  mb.cnt = m.cnt.p;
+  mb.flag = m.cnt.p + nblobs;
+  mb.nblobs = nblobs;
+  mb.min = p->min;
+  mb.max = p->max;
+
+  dsx_many_totals_t t{};
+  t.blobs = nblobs;
+  std::deque<std::vector<ManyRun>> runs;  // (kept until the call's last wait)
+  for (const ManyItem& it : items) {
+    if (c->cancel.load()) return DSX_E_INTERRUPTED;
+    uint64_t nonempty = 0;
+    for (uint64_t i = it.b0; i < it.b1; ++i) nonempty += blob_ends[i] != (i ? blob_ends[i - 1] : 0);
+    t.empty_blobs += it.b1 - it.b0 - nonempty;
+    if (it.end == it.start) continue;  // nothing but empty blobs
+    int rc;
+    if (it.single) {
+      rc = many_single(c, d_blob, mb, p, it.big, it.start, it.end);
+      t.single_blobs++;
+    } else {
+      runs.emplace_back();
+      rc = many_group(c, d_blob, mb, p, blob_ends, it, &runs.back());
+      t.groups++;
+      t.batched_blobs += nonempty;
+    }
+    if (rc) return rc;
+  }
+
+  ManyFinishArgs fa{};
+  fa.mb = mb;
+  fa.first = m.first.p;
+  fa.res = m.res.p;
+  uint64_t res[2] = {0, 0};
+  for (int round = 0; round < 2; ++round) {
+    hipLaunchKernelGGL(many_scan_kernel, dim3(1), dim3(kManyScanThreads), 0, c->stream, fa);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(res, m.res.p, sizeof(res), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!res[1]) break;
+    if (round == 1) {
+      c->err = "blobs still flagged after the one-blob path";
+      return DSX_E_INTERNAL;
+    }
+    // the batched walk could not hold these blobs (their candidates did not
+    // fit its LDS, or the group's scan overflowed a lane): the one-blob path
+    std::vector<uint32_t> flag(nblobs);
+    HIPCHK(c, hipMemcpy(flag.data(), mb.flag, nblobs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < nblobs; ++i) {
+      if (!flag[i]) continue;
+      if (c->cancel.load()) return DSX_E_INTERRUPTED;
+      const int rc = many_single(c, d_blob, mb, p, i, i ? blob_ends[i - 1] : 0, blob_ends[i]);
+      if (rc) return rc;
+      t.redone_blobs++;
+    }
+  }
+  t.chunks = res[0];
+  if (totals) *totals = t;
+  *n_out = res[0];
+  if (res[0] > cap) return DSX_E_CAPACITY;
+  if (res[0]) {
+    if (!dev_out) HIPCHK(c, grow(c, c->out, res[0]));
+    fa.out = dev_out ? out_ends : c->out.p;
+    hipLaunchKernelGGL(many_gather_kernel,
+                       dim3((uint32_t)((nblobs + kManyGatherThreads - 1) / kManyGatherThreads)),
+                       dim3(kManyGatherThreads), 0, c->stream, fa);
+    HIPCHK(c, hipGetLastError());
+    if (!dev_out)
+      HIPCHK(c, hipMemcpyAsync(out_ends, c->out.p, res[0] * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  if (blob_first)
+    HIPCHK(c, hipMemcpyAsync(blob_first, m.first.p, (nblobs + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->stats.chunks = res[0];
   return DSX_OK;
 }

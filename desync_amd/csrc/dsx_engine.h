@@ -15,6 +15,8 @@
 #include "../../include/dsx.h"
 #include "dsx_common.h"
 #include "dsx_digest.h"
+#include "dsx_many.h"
+#include "dsx_many_plan.h"
 #include "dsx_scan_geom.h"
 #include "dsx_stitch.h"
 
@@ -38,6 +40,9 @@ __global__ void finish_kernel(StitchArgs a);
 __global__ void gather_kernel(StitchArgs a);
 __global__ void publish_kernel(StitchArgs a);
 __global__ void noop_kernel();
+__global__ void many_walk_kernel(ManyWalkArgs a);
+__global__ void many_scan_kernel(ManyFinishArgs a);
+__global__ void many_gather_kernel(ManyFinishArgs a);
 __global__ void state_init_kernel(DevState* st, uint64_t carry);
 __global__ void gen_uniform_kernel(uint8_t* dst, uint64_t offset, uint64_t len, uint64_t seed);
 __global__ void gen_dedup_kernel(uint8_t* dst, uint64_t offset, uint64_t len, uint64_t seed,
@@ -327,6 +332,15 @@ struct dsx_ctx {
   hipEvent_t q_ev[kQueueDepth] = {};
   uint32_t q_next = 0;
 
+  // dsx_cut_device_many: the blob ends, the staging list,
+  // cnt[nblobs] + flag[nblobs], blob_first, the runs of the walk's workgroups
+  // and {total, flagged}
+  struct Many {
+    DevBuf<uint64_t> ends, stage, first, res;
+    DevBuf<uint32_t> cnt;
+    DevBuf<ManyRunDev> runs;
+  } many;
+
   IdsetScratch idset;  // chunk-ID sets (dsx_idset.hip)
   StoreScratch store;  // chunk stores (dsx_store.hip)
   AeadScratch aead;    // the AEAD store converter (dsx_aead.hip)
@@ -383,9 +397,30 @@ int read_state(dsx_ctx* c, HostState* out);
 // *pc_out (optional): the piece's candidate lists (shards: the seam window)
 int enqueue_piece(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo,
                   uint64_t P, uint64_t len, bool is_last, PieceCands* pc_out = nullptr);
+// The scan half of enqueue_piece: the piece's scan launch alone.  *so: what a
+// stitch over its candidate lists needs.  behind_tb (libdsx_diag.so, a call
+// stitched behind later scans): the tasks this scan carries.
+struct ScanOut {
+  PieceCands pc;
+  uint64_t seq = 0;
+  uint32_t pi = 0;  // the piece's index in the call (its timing events)
+  bool line = false;
+};
+int enqueue_scan(dsx_ctx* c, const CallCfg& cc, const uint8_t* d_piece, uint64_t halo, uint64_t P,
+                 uint64_t len, ScanOut* so, const TaskArgs* behind_tb = nullptr);
 // a whole device-resident blob [origin.., origin+len) through the engine
 int run_device(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, CallCfg cc);
 int ensure_attr_walk(dsx_ctx* c);
+// dsx_cut_device_many after its argument checks: many blobs packed in
+// d_blob[0, len), one cut list.  big_blob and group_bytes are
+// resolved (non-zero).
+int run_many(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, const uint64_t* blob_ends,
+             uint64_t nblobs, const dsx_params_t* p, uint64_t* out_ends, uint64_t cap,
+             uint64_t* n_out, uint64_t* blob_first, uint64_t big_blob, uint64_t group_bytes,
+             dsx_many_totals_t* totals, bool dev_out);
+uint64_t many_default_big_blob(const dsx_params_t* p);
+void many_release(dsx_ctx* c);
+uint64_t many_device_bytes(const dsx_ctx* c);
 // host threads (dsx_stream.cpp): fn(0) on the caller, fn(1..parts-1) on a
 // persistent pool; returns when all have returned
 void host_parallel(int parts, const std::function<void(int)>& fn);

@@ -110,33 +110,6 @@ __device__ __forceinline__ uint64_t next_cut(uint64_t s, Src& src, const ChainPa
 }
 
 // ---- K2: per-segment speculative walks ------------------------------------
-constexpr uint32_t kWalkMaxRegions = 4096;  // regions a walk workgroup can stage
-
-// Block-wide exclusive scan of one value per thread (NT threads); returns the
-// exclusive prefix, *total gets the block sum.
-template <int NT>
-__device__ uint32_t walk_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(incl, d, 64);
-    if (lane >= (uint32_t)d) incl += t;
-  }
-  if (lane == 63) s_wave[wv] = incl;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < NT / 64; ++i) {
-    const uint32_t t = s_wave[i];
-    before += (i < (int)wv) ? t : 0u;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - v;
-}
-
 // NT = 576 threads for 8 segments per workgroup (an 8 GiB piece: every chain
 // its own wave, so phase 1 is one chain long), 256 otherwise, or 1024 (split
 // streams: a few workgroups beside the next piece's scan, on the CUs it leaves

@@ -121,6 +121,153 @@ def cut_device_result(ctx=None):
     return n.value
 
 
+def cut_device_many(ptr, length, blob_ends, min_size, avg_size, max_size, ctx=None, out_ptr=None,
+                    out_cap=0, big_blob=0, group_bytes=0):
+    """Many blobs packed back to back in one device buffer -> one cut list whose
+    chain restarts at every blob boundary (dsx_cut_device_many).
+
+    ``blob_ends`` (host, non-decreasing, last == ``length``) delimits the
+    blobs.  Returns ``(ends, first, totals)``: the chunk ends in the packed
+    buffer's coordinates (a host np.uint64 array, or with ``out_ptr`` -- a
+    device buffer of ``out_cap`` uint64 -- the count), ``first`` (nblobs + 1:
+    blob i's chunks are ``ends[first[i]:first[i + 1]]``) and the call's
+    dsx_many_totals_t as a dict.  ``big_blob`` / ``group_bytes`` (0: the
+    library's defaults) change the cost, never the result.  Too small an
+    ``out_cap`` raises DsxError (DSX_E_CAPACITY) with ``.needed``."""
+    p = Params(min_size, avg_size, max_size)
+    ctx = ctx or _lib.default_context()
+    be = np.ascontiguousarray(blob_ends, dtype=np.uint64)
+    first = np.zeros(be.size + 1, dtype=np.uint64)
+    opts = _lib.ManyOpts(int(big_blob), int(group_bytes))
+    tot = _lib.ManyTotals()
+    n = ctypes.c_uint64()
+    if out_ptr is not None:
+        out, optr, cap, flags = None, int(out_ptr), int(out_cap), DSX_OUT_DEVICE
+    else:
+        cap = int(length) // int(min_size) + be.size
+        out = np.empty(max(1, cap), dtype=np.uint64)
+        optr, flags = out.ctypes.data, DSX_OUT_HOST
+    rc = lib().dsx_cut_device_many(ctx.h, ctypes.c_void_p(ptr), int(length),
+                                   ctypes.c_void_p(be.ctypes.data if be.size else None), be.size,
+                                   ctypes.byref(p.c), ctypes.c_void_p(optr), cap, ctypes.byref(n),
+                                   ctypes.c_void_p(first.ctypes.data), ctypes.byref(opts),
+                                   ctypes.byref(tot), flags)
+    if rc in (_lib.DSX_E_INVAL, _lib.DSX_E_CAPACITY):
+        d = lib().dsx_last_error(ctx.h) if rc == _lib.DSX_E_INVAL else None
+        e = _lib.DsxError(rc, d.decode() if d else "")
+        e.needed = n.value
+        raise e
+    if rc == _lib.DSX_E_INTERRUPTED:
+        raise Interrupted()
+    check(rc, ctx.h)
+    totals = {k: getattr(tot, k) for k, _ in _lib.ManyTotals._fields_ if k != "reserved"}
+    return (n.value if out is None else out[:n.value].copy()), first, totals
+
+
+class _DeviceBytes:
+    """A ``(pointer, length)`` pair as an object torch can view (no copy)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "|u1",
+                                         "data": (int(ptr), False), "version": 2}
+
+
+def _pack_blobs(blobs, ctx):
+    """-> (pointer, length, blob_ends, uint8 device tensor over the packed
+    bytes).  ``blobs`` is ``(buffer, blob_ends)`` with the buffer a device
+    tensor or a ``(pointer, length)`` pair, already packed; or a list of device
+    tensors and host bytes, which is packed here: one torch.cat of the device
+    tensors, one upload of the host bytes (a copy of every byte)."""
+    import torch
+    dev = f"cuda:{ctx.device}"
+    if isinstance(blobs, tuple):
+        buf, be = blobs
+        be = np.ascontiguousarray(be, dtype=np.uint64)
+        if isinstance(buf, tuple):
+            ptr, length = int(buf[0]), int(buf[1])
+            t = torch.as_tensor(_DeviceBytes(ptr, length), device=dev) if length else \
+                torch.empty(0, dtype=torch.uint8, device=dev)
+        else:
+            if not buf.is_contiguous():
+                raise ValueError("the packed buffer must be contiguous")
+            t = buf.view(torch.uint8).reshape(-1)
+            ptr, length = t.data_ptr(), t.numel()
+        return ptr, length, be, t
+    blobs = list(blobs)
+    host = [None if hasattr(b, "data_ptr") else bytes(b) for b in blobs]
+    lens = [len(h) if h is not None else b.numel() * b.element_size() for b, h in zip(blobs, host)]
+    be = np.cumsum(np.asarray(lens, dtype=np.uint64), dtype=np.uint64)
+    joined = b"".join(h for h in host if h is not None)
+    up = torch.frombuffer(bytearray(joined), dtype=torch.uint8).to(dev) if joined else \
+        torch.empty(0, dtype=torch.uint8, device=dev)
+    if all(h is not None for h in host):
+        t = up
+    else:
+        parts, at = [], 0
+        for b, h in zip(blobs, host):
+            if h is None:
+                parts.append(b.contiguous().view(torch.uint8).reshape(-1).to(dev))
+            else:
+                parts.append(up[at:at + len(h)])
+                at += len(h)
+        t = torch.cat(parts) if parts else up
+    torch.cuda.synchronize(t.device)  # (torch's stream, not the context's)
+    return t.data_ptr(), t.numel(), be, t
+
+
+def _blob_heads(t, starts, lens):
+    """The first 64 bytes of every blob of at least 64 bytes, in one gather:
+    -> {blob number: bytes} (the catar sniff of make.go:49-62)."""
+    import torch
+    which = np.flatnonzero(lens >= 64)
+    if which.size == 0:
+        return {}
+    idx = torch.from_numpy(starts[which].astype(np.int64)).to(t.device)[:, None] + \
+        torch.arange(64, device=t.device)[None, :]
+    heads = t[idx].cpu().numpy()
+    return {int(b): heads[k].tobytes() for k, b in enumerate(which)}
+
+
+def _index_blobs(blobs, min_size, avg_size, max_size, ctx):
+    """IndexFromBlobs' work: -> (indexes, pointer, length, global ends, ids,
+    tensor kept alive)."""
+    ctx = ctx or _lib.default_context()
+    ptr, length, be, t = _pack_blobs(blobs, ctx)
+    ends, first, _ = cut_device_many(ptr, length, be, min_size, avg_size, max_size, ctx=ctx)
+    ids = np.empty((ends.size, 32), dtype=np.uint8)
+    if ends.size:
+        check(lib().dsx_chunk_ids(ctx.h, ctypes.c_void_p(ptr), length, 0, ends.ctypes.data, ends.size,
+                                  ids.ctypes.data, 0, _digest_code()), ctx.h)
+    starts = np.concatenate([np.zeros(1, dtype=np.uint64), be[:-1]]) if be.size else be
+    heads = _blob_heads(t, starts, be - starts)
+    flags = CaFormatExcludeNoDump
+    if digest.Digest.Algorithm() == "sha512-256":
+        flags |= CaFormatSHA512256  # make.go:35-38
+    out = []
+    for i in range(be.size):
+        lo, hi = int(first[i]), int(first[i + 1])
+        ff = flags | catar_feature_flags(heads.get(i, b""))  # make.go:49-61
+        out.append(Index(FormatIndex(ff, min_size, avg_size, max_size),
+                         ChunkArray(ends[lo:hi] - starts[i], ids[lo:hi])))
+    return out, ptr, length, ends, ids, t
+
+
+def IndexFromBlobs(blobs, min_size, avg_size, max_size, ctx=None):
+    """IndexFromFile (make.go:22-163) for many blobs in HBM at once: one Index
+    per blob, each equal to what IndexFromFile gives for that blob's bytes
+    alone (chunk offsets relative to the blob; an empty blob gives the index
+    without chunks).
+
+    ``blobs`` is ``(buffer, blob_ends)`` -- the blobs already packed back to
+    back in a device tensor or a ``(pointer, length)`` pair -- or a list of
+    device tensors and host bytes.  A list is packed first, with one torch.cat
+    or one upload: that costs a copy of every byte.  Then one
+    dsx_cut_device_many call cuts every blob, one dsx_chunk_ids call hashes
+    every chunk, and one gather fetches each blob's first 64 bytes for the
+    catar flag sniff of make.go:49-62."""
+    return _index_blobs(blobs, min_size, avg_size, max_size, ctx)[0]
+
+
 def chunk_ids(ptr, length, ends, start=0, ctx=None, algo=None):
     """Digest.Sum of every chunk of a device-resident blob on the GPU
     (dsx_chunk_ids; digest.go:11-29, make.go:223).  ``ends`` is a host array of

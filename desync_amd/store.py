@@ -606,4 +606,20 @@ def ChopBlob(index, blob, store, verify=True):
     return store.put((ptr, length), ids, ends, 0)
 
 
-__all__ = ["DeviceStore", "ChopBlob", "OFF_NONE", "chunk_file_name", "chunk_id_from_filename"]
+def ChopBlobs(blobs, store, min_size, avg_size, max_size):
+    """``desync make -s`` over many blobs in HBM: :func:`IndexFromBlobs` (one
+    cut call and one hash call for all of them), then one ``put`` of every
+    chunk into ``store``, a :class:`DeviceStore`.  ``blobs`` as for
+    IndexFromBlobs (a list is packed first, which costs a copy).  The IDs were
+    just computed from the bytes, so nothing is re-hashed.  Returns the list of
+    indexes, one per blob (``store.counts()`` has the fill state)."""
+    from .make import _index_blobs
+    with store._lock:
+        indexes, ptr, length, ends, ids, _keep = _index_blobs(blobs, min_size, avg_size, max_size,
+                                                              store.ctx)
+        if len(ends):
+            store.put((ptr, length), ids, ends, 0)
+    return indexes
+
+
+__all__ = ["DeviceStore", "ChopBlob", "ChopBlobs", "OFF_NONE", "chunk_file_name", "chunk_id_from_filename"]

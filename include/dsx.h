@@ -144,6 +144,59 @@ int dsx_sync(dsx_ctx_t *ctx);
  * returns DSX_OK).  DSX_E_STATE if no call is queued. */
 int dsx_result(dsx_ctx_t *ctx, uint64_t *n_out);
 
+/* ---- many blobs in one call ---------------------------------------------------
+ * d_blob[0, len) holds nblobs blobs back to back (the files of a directory, the
+ * tensors of a checkpoint, the members of an archive).  blob_ends[nblobs] (host
+ * memory) is non-decreasing and its last entry is len; blob i is [B0, B1) =
+ * [blob_ends[i-1], blob_ends[i]) with blob_ends[-1] = 0.  Empty blobs are
+ * allowed and give no chunk.  One dsx_params_t applies to every blob.
+ * The result equals dsx_cut_device(d_blob + B0, B1 - B0) per blob with B0 added
+ * to its ends, concatenated in blob order: the chain of chunker.go:206-277
+ * restarts at every blob boundary, with B1 in the place of the length.  Every
+ * non-empty blob's B1 is in the list and the list is strictly increasing, so it
+ * is a valid `ends` argument (start = 0) for dsx_chunk_ids, dsx_store_put and
+ * dsx_aead_seal over the same buffer.  Blob i's chunks are
+ * out_ends[blob_first[i] .. blob_first[i+1]) and blob_first[nblobs] == *n_out.
+ * Small blobs are scanned in groups, one scan launch per group, and their chains
+ * are walked side by side; a blob of big_blob bytes or more takes the path of
+ * dsx_cut_device on its own.  The options change the cost, never
+ * the result.
+ * flags: DSX_OUT_HOST or DSX_OUT_DEVICE (where out_ends lives); any other bit,
+ * DSX_NO_SYNC included, is DSX_E_INVAL.  The call is synchronous.  If cap is too
+ * small it returns DSX_E_CAPACITY with the needed count in *n_out (totals is
+ * written, out_ends and blob_first are not); a capacity of len / min + nblobs
+ * always suffices.  nblobs == 0 with len == 0: DSX_OK, no chunk.
+ * Refused with DSX_E_INVAL before any device work (with a ctx, the reason is in
+ * dsx_last_error): a NULL ctx, p or n_out; NULL blob_ends with nblobs > 0; ends
+ * that decrease; a last end other than len; nblobs == 0 with len != 0; more than
+ * 2^32 - 16 blobs; a NULL d_blob with len > 0; a NULL out_ends with cap > 0;
+ * non-zero reserved option fields; group_bytes above 8 GiB.
+ * dsx_cancel is honoured between groups (DSX_E_INTERRUPTED).  Queued DSX_NO_SYNC
+ * calls of the context are treated as a synchronous dsx_cut_device treats them,
+ * and the context's one-blob calls behave as before after this call. */
+typedef struct dsx_many_opts {   /* 0 in a field: the library's default */
+    uint64_t big_blob;           /* blobs at least this long take the one-blob path (at most 1 GiB is
+                                    honoured; default: (4096 - 8) * discriminator, capped likewise) */
+    uint64_t group_bytes;        /* at most this many bytes per scan launch (<= 8 GiB, the default) */
+    uint64_t reserved[2];        /* must be 0 */
+} dsx_many_opts_t;
+
+typedef struct dsx_many_totals {
+    uint64_t blobs, empty_blobs, chunks;
+    uint64_t groups;             /* scan launches of the batched path */
+    uint64_t batched_blobs;      /* cut by the batched walk */
+    uint64_t single_blobs;       /* cut by the one-blob path because of big_blob or group_bytes */
+    uint64_t redone_blobs;       /* batched first, then re-run on the one-blob path */
+    uint64_t reserved;
+} dsx_many_totals_t;             /* 64 bytes */
+
+int dsx_cut_device_many(dsx_ctx_t *ctx, const void *d_blob, uint64_t len,
+                        const uint64_t *blob_ends, uint64_t nblobs, const dsx_params_t *p,
+                        uint64_t *out_ends, uint64_t cap, uint64_t *n_out,
+                        uint64_t *blob_first /* host, nblobs + 1, may be NULL */,
+                        const dsx_many_opts_t *opts /* may be NULL */,
+                        dsx_many_totals_t *totals /* may be NULL */, uint32_t flags);
+
 /* Host-memory blob -> cut list (host).  Pipelined pinned H2D inside. */
 int dsx_cut_host(dsx_ctx_t *ctx, const void *h_blob, uint64_t len, const dsx_params_t *p,
                  uint64_t *out_ends, uint64_t cap, uint64_t *n_out);
