@@ -1027,8 +1027,14 @@ extern "C" int dsx_shard_local(dsx_ctx_t* c, const void* d_shard, uint64_t halo,
     z.total = total;
     z.first_cand_beyond = UINT64_MAX;
     z.flags = shard_start == total ? DSX_SEAM_LAST : 0u;
+    HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, grow(c, c->d_seam, 1));
     HIPCHK(c, hipMemcpyAsync(c->d_seam.p, &z, sizeof z, hipMemcpyHostToDevice, c->stream));
+    // no chain runs: without this shard_emit_kernel would count the cuts of
+    // the context's previous call (st->total) as this shard's speculative ones
+    hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, c->stream, (DevState*)c->state.p,
+                       shard_start);
+    HIPCHK(c, hipGetLastError());
     sh.valid = true;
     return seam_out(c, seam, (flags & DSX_SEAM_DEVICE) != 0);
   }

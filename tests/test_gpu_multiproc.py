@@ -82,6 +82,7 @@ def test_shard_chunk_two_processes(kind):
     import torch.multiprocessing as mp
 
     from oracle import oracle as o
+    o.lib()  # loaded (on a fresh tree: built) once, before the ranks start
     data = _compose(kind)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

@@ -720,7 +720,7 @@ def _shard_protocol(data, world, dev):
     rounds = 0
     while True:
         rounds += 1
-        assert rounds <= world + 1
+        assert rounds <= world
         if dev:
             allrec = torch.cat(recs)
             torch.cuda.synchronize()

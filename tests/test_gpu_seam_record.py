@@ -516,21 +516,40 @@ def _zero_run(prm, seed=23):
                            np.zeros(100 * mx, np.uint8), o.synth_uniform(seed, 0, 4 * mx)])
 
 
-def _oracle_protocol(data, world, prm):
+def equal_spans(total, world):
+    span = total // world
+    return [(r * span, span if r < world - 1 else total - r * span) for r in range(world)]
+
+
+def geometry(bounds, total):
+    """(start, length) per rank from the inner shard boundaries (a boundary
+    given twice makes an empty shard)."""
+    edges = [0] + list(bounds) + [total]
+    return [(a, b - a) for a, b in zip(edges, edges[1:])]
+
+
+def _oracle_protocol(data, world, prm, geo=None):
     """The protocol on the CPU: per round the records every rank publishes
-    and oseam.resolve's outcome, then the final cuts per rank."""
+    and oseam.resolve's outcome, then the final cuts per rank.  `geo`: the
+    shards as (start, length), contiguous from 0 to data.size, lengths may be
+    0; the default is `world` equal spans.  The last round's outcome is
+    ("ok", [every rank's ext cuts])."""
     mn, av, mx = prm
     total = data.size
-    span = total // world
-    geo = [(r * span, span if r < world - 1 else total - r * span) for r in range(world)]
+    geo = equal_spans(total, world) if geo is None else [(int(s), int(n)) for s, n in geo]
+    assert len(geo) == world and geo[0][0] == 0 and sum(n for _, n in geo) == total
+    assert all(n >= 0 and s + n == s2 for (s, n), (s2, _) in zip(geo, geo[1:]))
     loc = [expect(data, s, n, total, mn, av, mx) for s, n in geo]
     seams, spec, cands = [x[0] for x in loc], [x[1] for x in loc], [x[2] for x in loc]
     rounds = []
     while True:
         outs = [oseam.resolve(seams, r, mn, mx) for r in range(world)]
-        rounds.append(([dict(s) for s in seams], outs[0][:1] if outs[0][0] == "ok" else outs[0]))
-        if outs[0][0] == "ok":
-            assert all(x[0] == "ok" for x in outs)
+        ok = outs[0][0] == "ok"
+        assert not ok or all(x[0] == "ok" for x in outs)
+        rounds.append(([dict(s) for s in seams], ("ok", [list(x[1]) for x in outs]) if ok else outs[0]))
+        if ok:
+            # (seam_resolve_kernel's ext holds DSX_SEAM_MAX_CUTS cuts and no more)
+            assert all(len(x[1]) < NCAP for x in outs)
             cuts = [oseam.rank_cuts(x[1], x[2], spec[r]) for r, x in enumerate(outs)]
             return geo, rounds, cuts
         assert all(x == outs[0] for x in outs) and len(rounds) <= world
@@ -539,22 +558,38 @@ def _oracle_protocol(data, world, prm):
         seams[r]["first_cand_beyond"] = U64_MAX
 
 
-def _protocol(data, world, dev, prm, min_rounds=1, pre=None):
-    """test_gpu_parity.py's _shard_protocol with the parameters given, every
-    round's records compared with oracle/seam.py's and every round's outcome
-    with oseam.resolve's."""
+def _protocol(data, world, variant, prm, min_rounds=1, pre=None, geo=None, oracle=None, ctxs=None,
+              t=None):
+    """test_gpu_parity.py's _shard_protocol with the parameters and the shard
+    geometry given (_oracle_protocol's `geo`), every round's records compared
+    with oracle/seam.py's and every round's outcome with oseam.resolve's.
+
+    variant: HOST (host records, dsx_shard_resolve), DEVICE (device records,
+    dsx_shard_resolve) or ASYNC: dsx_shard_local with DSX_SEAM_DEVICE |
+    DSX_NO_SYNC, then per round dsx_shard_resolve_async on every rank (device
+    cuts, a device code word) and dsx_shard_collect on every rank; the code
+    word must hold 0 after an ok round and 1 after a resync round, and the
+    final cuts are read from the device buffers.
+
+    oracle: _oracle_protocol's result, for a caller that has asserted its own
+    conditions on it; ctxs: `world` contexts to use (and leave open); t: the
+    blob on the device.  Returns (rounds, the cuts every rank got)."""
     import torch
     from desync_amd import _lib, shard
+    assert variant in VARIANTS
     L = _lib.lib()
     total = data.size
-    geo, rounds, want_cuts = _oracle_protocol(data, world, prm)
+    geo, rounds, want_cuts = oracle or _oracle_protocol(data, world, prm, geo)
     assert len(rounds) >= min_rounds
     assert np.array_equal(np.concatenate(want_cuts), o.chunk_stream(data, *prm))
     if pre:
         pre(rounds[0][0])
-    t = torch_dev(data)
+    t = torch_dev(data) if t is None else t
     p = _params(*prm)
-    ctxs = [_lib.Context(0) for _ in range(world)]
+    own = ctxs is None
+    ctxs = [_lib.Context(0) for _ in range(world)] if own else list(ctxs[:world])
+    assert len(ctxs) == world
+    dev = variant != HOST
     try:
         if dev:
             recs = [torch.empty(shard.SEAM_BYTES, dtype=torch.uint8, device="cuda") for _ in range(world)]
@@ -565,10 +600,18 @@ def _protocol(data, world, dev, prm, min_rounds=1, pre=None):
         sflag = _lib.DSX_SEAM_DEVICE if dev else 0
         for r, (start, length) in enumerate(geo):
             _lib.check(L.dsx_shard_local(ctxs[r].h, ctypes.c_void_p(t.data_ptr() + start),
-                                         64 if r else 0, start, length, total, ctypes.byref(p.c),
-                                         ctypes.c_void_p(ptr[r]), sflag), ctxs[r].h)
-        outs = [np.empty(length // prm[0] + 4 + NCAP, np.uint64) for _, length in geo]
+                                         64 if start else 0, start, length, total, ctypes.byref(p.c),
+                                         ctypes.c_void_p(ptr[r]), _flags(variant)), ctxs[r].h)
+        caps = [length // prm[0] + 4 + NCAP for _, length in geo]
         counts = [ctypes.c_uint64() for _ in range(world)]
+        if variant == ASYNC:
+            for c in ctxs:
+                _lib.check(L.dsx_sync(c.h), c.h)
+            outs = [torch.full((cap,), -1, dtype=torch.int64, device="cuda") for cap in caps]
+            codes = [torch.full((1,), 0x5A5A, dtype=torch.int32, device="cuda") for _ in range(world)]
+            agreed = ctypes.c_int32()
+        else:
+            outs = [np.empty(cap, np.uint64) for cap in caps]
         pieces = [c.stats().pieces for c in ctxs]
         for i, (seams, outcome) in enumerate(rounds):
             for r in range(world):
@@ -581,24 +624,42 @@ def _protocol(data, world, dev, prm, min_rounds=1, pre=None):
             else:
                 allrec = (_lib.Seam * world)(*recs)
                 aptr = ctypes.addressof(allrec)
-            rcs = [L.dsx_shard_resolve(ctxs[r].h, ctypes.c_void_p(aptr), world, r,
-                                       ctypes.c_void_p(ptr[r]), outs[r].ctypes.data, outs[r].size,
-                                       ctypes.byref(counts[r]), sflag) for r in range(world)]
+            if variant == ASYNC:
+                for r in range(world):
+                    codes[r].fill_(0x5A5A)
+                torch.cuda.synchronize()
+                for r in range(world):
+                    _lib.check(L.dsx_shard_resolve_async(
+                        ctxs[r].h, ctypes.c_void_p(aptr), world, r, ctypes.c_void_p(outs[r].data_ptr()),
+                        caps[r], ctypes.c_void_p(codes[r].data_ptr())), ctxs[r].h)
+                rcs = [L.dsx_shard_collect(ctxs[r].h, ctypes.c_void_p(ptr[r]), None, ctypes.byref(agreed),
+                                           ctypes.byref(counts[r])) for r in range(world)]
+                words = [int(c.item()) for c in codes]
+                assert words == [0 if outcome[0] == "ok" else 1] * world, (i + 1, words, outcome)
+            else:
+                rcs = [L.dsx_shard_resolve(ctxs[r].h, ctypes.c_void_p(aptr), world, r,
+                                           ctypes.c_void_p(ptr[r]), outs[r].ctypes.data, outs[r].size,
+                                           ctypes.byref(counts[r]), sflag) for r in range(world)]
             # (the rank and entry of oseam.resolve's ("resync", rank, entry) are
             # checked through the next round's records: only that rank's record is
             # rewritten, with DSX_SEAM_REWALKED and that entry)
             want_rc = 0 if outcome[0] == "ok" else _lib.DSX_E_RESYNC
             assert rcs == [want_rc] * world, (i + 1, rcs, outcome)
+        got_cuts = []
         for r in range(world):
-            got = outs[r][:counts[r].value]
+            n = counts[r].value
+            assert n <= caps[r], (r, n, caps[r])
+            got = outs[r][:n].cpu().numpy().astype(np.uint64) if variant == ASYNC else outs[r][:n].copy()
             assert np.array_equal(got, want_cuts[r]), (r, _first_diff(got.tolist(), want_cuts[r].tolist(),
                                                                      geo[r][0], "cuts"))
+            got_cuts.append(got)
         # a re-walk re-runs only the stitch over the kept candidate lists
         assert [c.stats().pieces for c in ctxs] == pieces
     finally:
-        for c in ctxs:
-            c.close()
-    return len(rounds)
+        if own:
+            for c in ctxs:
+                c.close()
+    return len(rounds), got_cuts
 
 
 @pytest.mark.parametrize("world,dev", [(3, False), (4, True)])
@@ -610,7 +671,7 @@ def test_protocol_candidate_capped_windows(world, dev):
         for s in seams[1:]:
             assert len(s["cands"]) == NCAP and s["window_end"] == s["cands"][-1]
 
-    _protocol(data, world, dev, SMALL, pre=pre)
+    _protocol(data, world, DEVICE if dev else HOST, SMALL, pre=pre)
 
 
 def test_protocol_planted_cut_cap():
@@ -621,7 +682,7 @@ def test_protocol_planted_cut_cap():
         assert seams[1]["shard_start"] % 200 not in (0, (SMALL[2] + 100) % 200)
         assert len(seams[0]["cuts"]) == NCAP and seams[0]["window_end"] == seams[0]["cuts"][-1]
 
-    _protocol(data, 2, False, SMALL, pre=pre)
+    _protocol(data, 2, HOST, SMALL, pre=pre)
 
 
 @pytest.mark.parametrize("world,dev", [(2, False), (4, True)])
@@ -631,4 +692,4 @@ def test_protocol_zero_run_rewalks(world, dev):
     oseam.rewalk's: DSX_SEAM_REWALKED, entry, exit_cut, empty lists."""
     data = _zero_run(MID)
     _no_candidate_at_48(data, *MID)
-    assert _protocol(data, world, dev, MID, min_rounds=2) > 1
+    assert _protocol(data, world, DEVICE if dev else HOST, MID, min_rounds=2)[0] > 1

@@ -1,4 +1,4 @@
-"""N>1 path on CPU: world_size 2 and 3 "gloo" processes run desync_amd.shard's
+"""N>1 path on CPU: world_size 2, 3 and 8 "gloo" processes run desync_amd.shard's
 seam_protocol -- the exchange / resolve / re-walk loop every transport of
 the product shares -- with an engine that restates the two library calls on
 the CPU (oracle/seam.py).  The concatenated per-rank cut lists must equal the
@@ -22,6 +22,37 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def _equal_spans(total, world):
+    span = total // world
+    return [(r * span, span if r < world - 1 else total - r * span) for r in range(world)]
+
+
+def _geometry(bounds, total):
+    """(start, length) per rank from the inner shard boundaries (a boundary
+    given twice makes an empty shard)."""
+    edges = [0] + list(bounds) + [total]
+    return [(a, b - a) for a, b in zip(edges, edges[1:])]
+
+
+def _oracle_rounds(data, world, geo=None):
+    """The protocol in one process over oracle/seam.py: (the number of
+    exchange rounds, the concatenated cuts, the ranks that re-walked)."""
+    from oracle import seam as oseam
+    geo = geo or _equal_spans(data.size, world)
+    loc = [oseam.shard_local(data, s, n, data.size, MIN, AVG, MAX) for s, n in geo]
+    seams, spec, cands = [x[0] for x in loc], [x[1] for x in loc], [x[2] for x in loc]
+    rewalked = []
+    for rounds in range(1, world + 1):
+        outs = [oseam.resolve(seams, r, MIN, MAX) for r in range(world)]
+        if outs[0][0] == "ok":
+            return rounds, sum((oseam.rank_cuts(x[1], x[2], spec[r]).tolist()
+                                for r, x in enumerate(outs)), []), rewalked
+        _, r, entry = outs[0]
+        rewalked.append(r)
+        seams[r], spec[r] = oseam.rewalk(cands[r], entry, geo[r][0], geo[r][1], data.size, MIN, MAX)
+    raise AssertionError("the oracle's protocol did not settle within nranks rounds")
 
 
 def _to_struct(seam):
@@ -51,14 +82,11 @@ class OracleEngine:
     restated on the CPU (oracle/seam.py); records are the dsx_seam_t bytes
     the library exchanges."""
 
-    def __init__(self, data, rank, world, fail_at=None):
+    def __init__(self, data, rank, world, fail_at=None, geo=None):
         from desync_amd import shard
         self.sh = shard
         self.data, self.rank, self.world = data, rank, world
-        total = data.size
-        span = total // world
-        self.start = rank * span
-        self.length = span if rank < world - 1 else total - self.start
+        self.start, self.length = (geo or _equal_spans(data.size, world))[rank]
         self.fail_at = fail_at
         self.rounds = 0
 
@@ -108,8 +136,8 @@ class OracleDeviceEngine(OracleEngine):
     collect, as over host-staged records.  ``fail`` injects a failure in
     start, resolve or the re-walk."""
 
-    def __init__(self, data, rank, world, fail=None, device_agree=True):
-        super().__init__(data, rank, world)
+    def __init__(self, data, rank, world, fail=None, device_agree=True, geo=None):
+        super().__init__(data, rank, world, geo=geo)
         self.fail, self.device_agree = fail, device_agree
         self.recb = None
 
@@ -170,14 +198,14 @@ class OracleDeviceEngine(OracleEngine):
         return "resync", agreed
 
 
-def _worker(rank, world, port, data, result_q, fail_rank):
+def _worker(rank, world, port, data, result_q, fail_rank, geo=None):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch.distributed as dist
     from desync_amd import shard
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    eng = OracleEngine(data, rank, world, fail_at=1 if rank == fail_rank else None)
+    eng = OracleEngine(data, rank, world, fail_at=1 if rank == fail_rank else None, geo=geo)
     try:
         mine = shard.seam_protocol(eng, world)
         out = [None] * world
@@ -207,11 +235,20 @@ def _compose(kind):
     return np.concatenate([r1, null, null, null, r1, null, null, null, r2])
 
 
-def _run(data, world, fail_rank=None):
+def _load_oracle():
+    """The oracle library, loaded (and on a fresh tree built) in the parent:
+    otherwise every spawned rank that finds it missing runs make on the one
+    output file at the same time."""
+    from oracle import oracle as o
+    o.lib()
+
+
+def _run(data, world, fail_rank=None, geo=None):
+    _load_oracle()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, data, q, fail_rank))
+    procs = [ctx.Process(target=_worker, args=(r, world, port, data, q, fail_rank, geo))
              for r in range(world)]
     for p in procs:
         p.start()
@@ -222,8 +259,8 @@ def _run(data, world, fail_rank=None):
     return msgs
 
 
-@pytest.mark.parametrize("kind", ["random", "spread-null", "seam-zero-run"])
-@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("world,kind", [(w, k) for k in ("random", "spread-null", "seam-zero-run")
+                                        for w in (2, 3)] + [(8, "seam-zero-run")])
 def test_seam_protocol_gloo(kind, world):
     from oracle import oracle as o
     data = _compose(kind)
@@ -232,6 +269,33 @@ def test_seam_protocol_gloo(kind, world):
     assert got == o.chunk_stream(data, MIN, AVG, MAX).tolist()
     if kind == "seam-zero-run":
         assert rounds > 1  # the re-walk path ran
+    if world == 8:  # a cascade: one rank re-walks per round, ranks 1 to 6 in turn
+        want_rounds, _, rewalked = _oracle_rounds(data, world)
+        assert rounds == want_rounds == world - 1 and rewalked == list(range(1, world - 1))
+
+
+def test_seam_protocol_gloo_short_shards():
+    """8 ranks over test_gpu_seam_worlds.py's "short shards in zeros" (there
+    at 1024/4096/16384): non-final shards of 5000 bytes inside the zero run,
+    shorter than min, that hold no cut and are re-walked, whose entry the
+    next rank's passes through; an empty shard between them; a chunk that
+    spans four shards."""
+    from oracle import oracle as o
+    data = _compose("seam-zero-run")
+    z0 = 3 * MAX + 12345  # the first zero
+    geo = _geometry([40000, z0 + 3000, z0 + 8000, z0 + 13000, z0 + 18000, z0 + 18000,
+                     z0 + 18000 + 40 * MAX], data.size)
+    ref = o.chunk_stream(data, MIN, AVG, MAX).tolist()
+    want_rounds, cuts, rewalked = _oracle_rounds(data, 8, geo)
+    assert cuts == ref and want_rounds >= 5
+    assert geo[5][1] == 0 and all(0 < n < MIN for _, n in geo[2:5])
+    # the short shards re-walk; the empty one has no seam of its own to
+    # converge (resolve's shard_len == 0 branches) and is never asked to
+    assert {2, 3, 4} <= set(rewalked) and 5 not in rewalked
+    (st, got, rounds), = _run(data, 8, geo=geo)
+    assert st == "ok"
+    assert got == ref
+    assert rounds == want_rounds
 
 
 @pytest.mark.parametrize("kind", ["seam-zero-run", "random"])
@@ -267,6 +331,7 @@ def _dworker(rank, world, port, data, result_q, fail_rank, fail, device_agree):
 
 
 def _drun(data, world, fail_rank=None, fail=None, device_agree=True):
+    _load_oracle()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -284,7 +349,7 @@ def _drun(data, world, fail_rank=None, fail=None, device_agree=True):
 
 @pytest.mark.parametrize("device_agree", [True, False])
 @pytest.mark.parametrize("kind,world", [("random", 2), ("seam-zero-run", 2), ("seam-zero-run", 3),
-                                        ("spread-null", 3)])
+                                        ("spread-null", 3), ("seam-zero-run", 8)])
 def test_device_protocol_gloo(kind, world, device_agree):
     """DeviceShard's asynchronous loop (one host wait per converged step)
     gives the sequential chunker's cut list, re-walks included."""
@@ -295,13 +360,17 @@ def test_device_protocol_gloo(kind, world, device_agree):
     assert got == o.chunk_stream(data, MIN, AVG, MAX).tolist()
     if kind == "seam-zero-run":
         assert rounds > 1
+    if world == 8:
+        assert rounds == _oracle_rounds(data, world)[0] == world - 1
 
 
-@pytest.mark.parametrize("device_agree", [True, False])
-@pytest.mark.parametrize("fail,world,fail_rank", [("start", 2, 0), ("start", 3, 2),
-                                                  ("resolve", 3, 1), ("rewalk", 2, 1),
-                                                  ("rewalk", 3, 1), ("capacity", 2, 1),
-                                                  ("capacity", 3, 0)])
+@pytest.mark.parametrize("fail,world,fail_rank,device_agree",
+                         [f + (agree,) for agree in (True, False)
+                          for f in (("start", 2, 0), ("start", 3, 2), ("resolve", 3, 1),
+                                    ("rewalk", 2, 1), ("rewalk", 3, 1), ("capacity", 2, 1),
+                                    ("capacity", 3, 0))]
+                         # rank 5 is the fifth to re-walk: its failure comes in round 5
+                         + [("rewalk", 8, 5, True)])
 def test_device_protocol_failure_propagates(fail, world, fail_rank, device_agree):
     """A rank failing before its round code is known (start, resolve) or after
     the device agreement (its re-walk, on a zero run across every seam), or
