@@ -35,7 +35,7 @@ from .chop import ChopFile  # noqa: F401
 from .hash import Hash, NewHash  # noqa: F401
 from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
-    Segment  # noqa: F401
+    Segment, StorageError  # noqa: F401
 from .store import ChopBlob, ChopBlobs, DeviceStore  # noqa: F401
 from .copy import Cache, Copy, NewCache  # noqa: F401
 from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
@@ -52,4 +52,5 @@ __all__ = [
     "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing", "Copy", "Cache", "NewCache",
     "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
     "StoreOptions", "AuthenticationError", "IndexFromBlobs", "ChopBlobs", "cut_device_many",
+    "StorageError",
 ]

@@ -63,6 +63,7 @@ EXPORTS = (
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
     "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305", "dsx_cut_device_many",
+    "dsx_inplace_plan", "dsx_assemble_inplace", "dsx_chunk_keep",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -73,10 +74,16 @@ DSX_SIZES = 64
 DSX_POS_NONE = 0xFFFFFFFF  # seed_pos of an ID the seed does not hold
 DSX_SRC_NULL = -1          # dsx_plan_seg_t.source: the null seed
 DSX_SRC_STORE = -2         # ... the packed store buffer
+DSX_SRC_SELF = -3          # ... the buffer's own old content (dsx_assemble_inplace)
+DSX_SRC_STASH = -4         # ... the stash (in a schedule's launch tables only)
 DSX_STORE_DEVICE = 128
 DSX_ASSEMBLE_UNALIGNED = 256
 DSX_PRUNE_REMOVE = 512
 DSX_COPY_ALL = 1024
+DSX_INPLACE_ASCENDING = 2048
+DSX_INPLACE_DESCENDING = 4096
+DSX_INPLACE_SAVE = 0       # dsx_inplace_launch_t.kind
+DSX_INPLACE_WRITE = 1
 DSX_ASSEMBLE_TILE = 65536
 DSX_AEAD_XCHACHA20_POLY1305 = 0
 DSX_AEAD_NONCE = 24
@@ -129,6 +136,23 @@ class PlanTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("segments", "seed_chunks", "seed_bytes", "null_chunks", "null_bytes",
                  "store_chunks", "store_bytes", "store_unique", "store_len")]
+
+
+class InplaceLaunch(ctypes.Structure):
+    """dsx_inplace_launch_t: one launch of an in-place schedule."""
+
+    _fields_ = [("window", ctypes.c_uint64), ("seg0", ctypes.c_uint64), ("nsegs", ctypes.c_uint64),
+                ("lo", ctypes.c_uint64), ("hi", ctypes.c_uint64), ("kind", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class InplaceTotals(ctypes.Structure):
+    """dsx_inplace_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("windows", "launches", "segments", "kept_chunks", "kept_bytes", "written_bytes",
+                 "stash_bytes", "stash_peak")] + [("direction", ctypes.c_uint32),
+                                                  ("reserved", ctypes.c_uint32)]
 
 
 class StoreCounts(ctypes.Structure):
@@ -337,6 +361,11 @@ def lib():
             "dsx_seed_plan": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, u32, vp, u32, vp, u64, vp, u64,
                                     P(PlanTotals), u32]),
             "dsx_assemble": (i32, [vp, vp, u64, vp, vp, u32, vp, u64, vp, u64, u32]),
+            "dsx_inplace_plan": (i32, [vp, u64, vp, u64, vp, u64, u64, u64, u64, u64, u64, u32, vp,
+                                       u64, vp, u64, P(InplaceTotals)]),
+            "dsx_assemble_inplace": (i32, [vp, vp, u64, vp, u64, vp, vp, vp, u32, vp, u64, vp, u64,
+                                           u64, u64, u64, u64, u32, P(InplaceTotals)]),
+            "dsx_chunk_keep": (i32, [vp, vp, u64, vp, u64, vp, i32, vp, P(u64), u32]),
             "dsx_store_create": (i32, [vp, u64, u64, P(vp)]),
             "dsx_store_destroy": (i32, [vp, vp]),
             "dsx_store_count": (i32, [vp, P(StoreCounts)]),

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "dsx_engine.h"
+#include "dsx_inplace_plan.h"
 
 namespace dsx {
 
@@ -268,4 +269,228 @@ extern "C" int dsx_assemble(dsx_ctx_t* c, const dsx_plan_seg_t* segs, uint64_t n
   } catch (const std::bad_alloc&) {
     return DSX_E_NOMEM;
   }
+}
+
+// ---- in place ("In place") -------------------------------------
+// The schedule is dsx_inplace_plan.h's: every launch below is assemble_kernel
+// over a table whose read ranges and write ranges the host has proved
+// disjoint, and the kernel reads no byte outside a piece's source range, so
+// stream order between the launches is the only synchronisation there is.
+namespace {
+
+constexpr uint64_t kInplaceWindow = 128ull << 20;
+
+int partial(dsx_ctx* c, int rc, bool wrote) {
+  if (rc && wrote) c->err += "; the buffer holds a partial update";
+  return rc;
+}
+
+int run_inplace(dsx_ctx* c, const dsx_host::InplacePlan& plan, const std::vector<AsmSeg>& dev,
+                void* d_buf, uint64_t new_len, bool unaligned, bool* wrote) {
+  IdsetScratch& t = c->idset;
+  HIPCHK(c, grow(c, t.asm_segs, 3 * dev.size()));
+  HIPCHK(c, hipMemcpyAsync(t.asm_segs.p, dev.data(), dev.size() * sizeof(AsmSeg),
+                           hipMemcpyHostToDevice, c->stream));
+  const AsmSeg* d_segs = reinterpret_cast<const AsmSeg*>(t.asm_segs.p);
+  for (const dsx_inplace_launch_t& l : plan.launches) {
+    const bool save = l.kind == DSX_INPLACE_SAVE;
+    const int rc = assemble_launch(c, d_segs + l.seg0, l.nsegs, save ? (void*)t.asm_stash.p : d_buf,
+                                   save ? plan.totals.stash_peak : new_len, l.lo, l.hi, unaligned);
+    if (rc) return rc;
+    if (!save) *wrote = true;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return DSX_OK;
+}
+
+}  // namespace
+
+extern "C" int dsx_assemble_inplace(dsx_ctx_t* c, const dsx_plan_seg_t* segs, uint64_t nsegs,
+                                    const uint64_t* ends, uint64_t n, const uint8_t* keep,
+                                    const void* const* d_seeds, const uint64_t* seed_lens,
+                                    uint32_t nseeds, const void* store, uint64_t store_len,
+                                    void* d_buf, uint64_t buf_cap, uint64_t have_len,
+                                    uint64_t new_len, uint64_t window, uint64_t stash_cap,
+                                    uint32_t flags, dsx_inplace_totals_t* totals) {
+  DSX_FLUSH_BEHIND(c);
+  const uint32_t f_store = DSX_STORE_DEVICE, f_unal = DSX_ASSEMBLE_UNALIGNED;
+  const uint32_t f_dir = DSX_INPLACE_ASCENDING | DSX_INPLACE_DESCENDING;
+  if (!c || (flags & ~(f_store | f_unal | f_dir)) != 0) return DSX_E_INVAL;
+  if ((nsegs && !segs) || (n && !ends) || (buf_cap && !d_buf) || (store_len && !store))
+    return DSX_E_INVAL;
+  if (nseeds && (!d_seeds || !seed_lens)) return DSX_E_INVAL;
+  if (buf_cap > UINT64_MAX - (uintptr_t)d_buf) return DSX_E_INVAL;
+  c->err.clear();
+  if (totals) *totals = dsx_inplace_totals_t{};
+  // ---- every check comes before any launch -----------------------------------
+  if (new_len > buf_cap || have_len > buf_cap) {
+    c->err = new_len > buf_cap ? "new_len is beyond the buffer's capacity"
+                               : "have_len is beyond the buffer's capacity";
+    return DSX_E_INVAL;
+  }
+  for (uint32_t k = 0; k < nseeds; ++k) {
+    if (seed_lens[k] && !d_seeds[k]) return DSX_E_INVAL;
+    if (overlaps(d_buf, buf_cap, d_seeds[k], seed_lens[k])) {
+      c->err = "the buffer overlaps seed " + std::to_string(k);
+      return DSX_E_INVAL;
+    }
+  }
+  const bool store_dev = (flags & f_store) != 0;
+  if (store_dev && overlaps(d_buf, buf_cap, store, store_len)) {
+    c->err = "the buffer overlaps the store buffer";
+    return DSX_E_INVAL;
+  }
+  for (uint64_t i = 0; i < nsegs; ++i) {
+    const dsx_plan_seg_t& g = segs[i];
+    uint64_t src_len = 0;
+    if (g.source >= 0) {
+      if ((uint32_t)g.source >= nseeds) return seg_error(c, i, "source names no seed");
+      src_len = seed_lens[g.source];
+    } else if (g.source == DSX_SRC_STORE) {
+      src_len = store_len;
+    } else if (g.source != DSX_SRC_NULL && g.source != DSX_SRC_SELF) {
+      return seg_error(c, i, "source is neither a seed, the null seed, the store nor the buffer");
+    }
+    if ((g.source >= 0 || g.source == DSX_SRC_STORE) &&
+        (g.bytes > src_len || g.src_off > src_len - g.bytes))
+      return seg_error(c, i, "src_off + bytes is beyond its source");
+  }
+  if (!window) window = kInplaceWindow;
+  if (!stash_cap) stash_cap = window > UINT64_MAX / 2 ? UINT64_MAX : 2 * window;
+  try {
+    dsx_host::InplacePlan plan;
+    const int prc = dsx_host::inplace_plan(segs, nsegs, ends, n, keep, have_len, new_len,
+                                           (uintptr_t)d_buf & 15, kAsmTile, window, stash_cap,
+                                           flags & f_dir, &plan);
+    if (prc == DSX_E_INVAL) {
+      if (plan.bad_seg != UINT64_MAX) return seg_error(c, plan.bad_seg, plan.why);
+      c->err = plan.why;
+      return prc;
+    }
+    if (totals) *totals = plan.totals;
+    if (prc == DSX_E_CAPACITY)
+      c->err = "the stash takes " + std::to_string(plan.totals.stash_peak) + " bytes";
+    if (prc || plan.launches.empty()) return prc;
+
+    HIPCHK(c, hipSetDevice(c->device));
+    IdsetScratch& t = c->idset;
+    hipStream_t st = c->stream;
+    if (!store_dev && store_len) {
+      HIPCHK(c, grow(c, t.asm_store, store_len));
+      HIPCHK(c, hipMemcpyAsync(t.asm_store.p, store, store_len, hipMemcpyHostToDevice, st));
+      store = t.asm_store.p;
+    }
+    if (t.asm_stash.n < plan.totals.stash_peak || !t.asm_stash.p) {
+      HIPCHK(c, hipStreamSynchronize(st));  // (work in flight may still read the old one)
+      HIPCHK(c, t.asm_stash.ensure(plan.totals.stash_peak));
+    }
+    std::vector<AsmSeg> dev(plan.segs.size());
+    for (size_t i = 0; i < dev.size(); ++i) {
+      const dsx_plan_seg_t& g = plan.segs[i];
+      const uint8_t* base = g.source >= 0                 ? (const uint8_t*)d_seeds[g.source]
+                            : g.source == DSX_SRC_STORE   ? (const uint8_t*)store
+                            : g.source == DSX_SRC_SELF    ? (const uint8_t*)d_buf
+                            : g.source == DSX_SRC_STASH   ? t.asm_stash.p
+                                                          : nullptr;
+      dev[i].dst_off = g.dst_off;
+      dev[i].bytes = g.bytes;
+      dev[i].src = base ? base + g.src_off : nullptr;
+      if (!base && g.source != DSX_SRC_NULL) {
+        c->err = "a source without memory";
+        return DSX_E_INTERNAL;
+      }
+    }
+    bool wrote = false;
+    return partial(c, run_inplace(c, plan, dev, d_buf, new_len, (flags & f_unal) != 0, &wrote), wrote);
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
+}
+
+// ---- which chunks already lie at their place (assemble.go:38-48) ---------------
+namespace dsx {
+
+// One lane per chunk: the 32 bytes the digest kernel left for chunk i against
+// the wanted ID, where both lie.  A chunk that reaches beyond have_len (the
+// digest kernel gave it no ID) is not kept.  One atomic per wave.
+__global__ __launch_bounds__(256) void id_match_kernel(const uint8_t* got, const uint8_t* want,
+                                                       const uint64_t* ends, u64 n, u64 have_len,
+                                                       uint8_t* keep, unsigned long long* count) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  bool same = false;
+  if (i < n) {
+    const u64 s = i ? ends[i - 1] : 0, e = ends[i];
+    same = s <= e && e <= have_len;
+    if (same) {
+      const uint4* a = reinterpret_cast<const uint4*>(got + 32 * i);
+      const uint4 a0 = a[0], a1 = a[1];
+      uint32_t w[8];  // (a caller's IDs need not be aligned)
+      __builtin_memcpy(w, want + 32 * i, 32);
+      same = a0.x == w[0] && a0.y == w[1] && a0.z == w[2] && a0.w == w[3] && a1.x == w[4] &&
+             a1.y == w[5] && a1.z == w[6] && a1.w == w[7];
+    }
+    keep[i] = same ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(same);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, (unsigned long long)__popcll(m));
+}
+
+}  // namespace dsx
+
+extern "C" int dsx_chunk_keep(dsx_ctx_t* c, const void* d_buf, uint64_t have_len,
+                              const uint64_t* ends, uint64_t n, const void* ids, int algo,
+                              uint8_t* keep, uint64_t* n_kept, uint32_t flags) {
+  DSX_FLUSH_BEHIND(c);
+  if (!c || (algo != DSX_DIGEST_SHA512_256 && algo != DSX_DIGEST_SHA256)) return DSX_E_INVAL;
+  if ((flags & ~(DSX_IDS_DEVICE | DSX_ENDS_DEVICE)) != 0) return DSX_E_INVAL;
+  if ((n && (!ends || !ids || !keep)) || (have_len && !d_buf)) return DSX_E_INVAL;
+  if (n_kept) *n_kept = 0;
+  if (n == 0) return DSX_OK;
+  if (n > 0xFFFFFFF0ull) return DSX_E_INVAL;
+  c->err.clear();
+  if (!(flags & DSX_ENDS_DEVICE)) {
+    for (uint64_t i = 1; i < n; ++i)
+      if (ends[i] < ends[i - 1]) {
+        c->err = "chunk ends must be non-decreasing";
+        return DSX_E_INVAL;
+      }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  IdsetScratch& t = c->idset;
+  const uint64_t* d_ends = ends;
+  if (!(flags & DSX_ENDS_DEVICE)) {
+    HIPCHK(c, grow(c, c->dg_ends, n));
+    HIPCHK(c, hipMemcpyAsync(c->dg_ends.p, ends, n * 8, hipMemcpyHostToDevice, st));
+    d_ends = c->dg_ends.p;
+  }
+  const uint8_t* d_want = (const uint8_t*)ids;
+  if (!(flags & DSX_IDS_DEVICE)) {
+    HIPCHK(c, grow(c, t.ids, n * 32));
+    HIPCHK(c, hipMemcpyAsync(t.ids.p, ids, n * 32, hipMemcpyHostToDevice, st));
+    d_want = t.ids.p;
+  }
+  HIPCHK(c, grow(c, c->dg_ids, n * 32));
+  HIPCHK(c, grow(c, t.is_null, n));  // (the keep bytes: one per target chunk, as is_null is)
+  HIPCHK(c, grow(c, t.tot, kIdsetCounters));
+  HIPCHK(c, hipMemsetAsync(t.tot.p, 0, 8, st));
+  DigestArgs da{};
+  da.blob = (const uint8_t*)d_buf;
+  da.len = have_len;
+  da.ends = d_ends;
+  da.first_start = 0;
+  da.n = n;
+  da.ids = c->dg_ids.p;
+  const int rc = launch_digest(c, da, n, algo);
+  if (rc) return rc;
+  hipLaunchKernelGGL(id_match_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st,
+                     (const uint8_t*)c->dg_ids.p, d_want, d_ends, (u64)n, (u64)have_len,
+                     t.is_null.p, t.tot.p);
+  HIPCHK(c, hipGetLastError());
+  unsigned long long kept = 0;
+  HIPCHK(c, hipMemcpyAsync(keep, t.is_null.p, n, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&kept, t.tot.p, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_kept) *n_kept = kept;
+  return DSX_OK;
 }

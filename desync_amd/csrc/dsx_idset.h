@@ -39,6 +39,7 @@ struct IdsetScratch {
   DevBuf<uint8_t> is_null;         // one byte per target chunk
   DevBuf<uint64_t> asm_segs;       // the plan as the gather kernel reads it (3 words a segment)
   DevBuf<uint8_t> asm_store;       // the staged copy of host store bytes
+  DevBuf<uint8_t> asm_stash;       // dsx_assemble_inplace: old bytes out of the way of a window's writes
 };
 
 // One segment as the gather kernel reads it (dsx_assemble.hip).

@@ -179,7 +179,7 @@ void free_set(dsx_idset* s) {
 uint64_t idset_device_bytes(const dsx_ctx* c) {
   const IdsetScratch& t = c->idset;
   uint64_t b = t.slots.n * 4 + t.ids.n + t.ends.n * 8 + t.first_pos.n * 4 + t.seed_pos.n * 4 +
-               t.tot.n * 8 + t.is_null.n + t.asm_segs.n * 8 + t.asm_store.n;
+               t.tot.n * 8 + t.is_null.n + t.asm_segs.n * 8 + t.asm_store.n + t.asm_stash.n;
   for (const dsx_idset* s : t.live) b += s->ids.n + s->slots.n * 4 + s->sclass.n * 4;
   return b;
 }
@@ -187,7 +187,7 @@ uint64_t idset_device_bytes(const dsx_ctx* c) {
 void idset_release(dsx_ctx* c) {
   IdsetScratch& t = c->idset;
   t.slots.release(), t.ids.release(), t.ends.release(), t.first_pos.release(), t.seed_pos.release();
-  t.tot.release(), t.is_null.release(), t.asm_segs.release(), t.asm_store.release();
+  t.tot.release(), t.is_null.release(), t.asm_segs.release(), t.asm_store.release(), t.asm_stash.release();
   for (dsx_idset* s : t.live) free_set(s);
   t.live.clear();
 }

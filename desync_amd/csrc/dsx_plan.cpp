@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/dsx.h"
+#include "dsx_inplace_plan.h"
 
 namespace {
 
@@ -205,6 +206,31 @@ extern "C" int dsx_plan_walk(const uint64_t* ends, uint64_t start, uint64_t n,
     }
     *totals = t;
     return (t.segments > seg_cap || t.store_unique > store_cap) ? DSX_E_CAPACITY : DSX_OK;
+  } catch (const std::bad_alloc&) {
+    return DSX_E_NOMEM;
+  }
+}
+
+// The schedule of an in-place assembly (dsx_inplace_plan.h) through the C ABI.
+extern "C" int dsx_inplace_plan(const dsx_plan_seg_t* segs, uint64_t nsegs, const uint64_t* ends,
+                                uint64_t n, const uint8_t* keep, uint64_t have_len,
+                                uint64_t new_len, uint64_t skew, uint64_t tile, uint64_t window,
+                                uint64_t stash_cap, uint32_t flags, dsx_inplace_launch_t* launches,
+                                uint64_t launch_cap, dsx_plan_seg_t* out_segs, uint64_t seg_cap,
+                                dsx_inplace_totals_t* totals) {
+  if (!totals || (launch_cap && !launches) || (seg_cap && !out_segs)) return DSX_E_INVAL;
+  *totals = dsx_inplace_totals_t{};
+  try {
+    dsx_host::InplacePlan plan;
+    const int rc = dsx_host::inplace_plan(segs, nsegs, ends, n, keep, have_len, new_len, skew, tile,
+                                          window, stash_cap, flags, &plan);
+    if (rc == DSX_E_INVAL) return rc;
+    *totals = plan.totals;
+    if (rc) return rc;
+    if (plan.launches.size() > launch_cap || plan.segs.size() > seg_cap) return DSX_E_CAPACITY;
+    std::copy(plan.launches.begin(), plan.launches.end(), launches);
+    std::copy(plan.segs.begin(), plan.segs.end(), out_segs);
+    return DSX_OK;
   } catch (const std::bad_alloc&) {
     return DSX_E_NOMEM;
   }

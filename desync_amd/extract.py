@@ -38,6 +38,7 @@ Segment.__doc__ = """One plan entry (SeedSegmentCandidate, sequencer.go:21-25): 
 (>= 0, chunk ``seed_first`` on, byte ``src_off`` of its blob), the null seed (SRC_NULL) or the
 packed store buffer at ``src_off`` (SRC_STORE)."""
 SRC_NULL, SRC_STORE = DSX_SRC_NULL, DSX_SRC_STORE
+SRC_SELF = _lib.DSX_SRC_SELF  # in-place assembly: the output buffer's own old content
 
 
 class SeedInvalid(Exception):
@@ -46,6 +47,15 @@ class SeedInvalid(Exception):
     def __init__(self, seed, number):
         self.seed, self.number = seed, number
         super().__init__(f"seed index for seed {number} doesn't match its data")
+
+
+class StorageError(DsxError):
+    """An in-place assembly that its stash cannot hold (DSX_E_CAPACITY):
+    ``.needed`` is the stash it takes, ``.totals`` the call's totals."""
+
+    def __init__(self, needed, totals):
+        super().__init__(_lib.DSX_E_CAPACITY, f"the stash takes {needed} bytes")
+        self.needed, self.totals = int(needed), totals
 
 
 def _check(rc, ctx):
@@ -254,12 +264,11 @@ def NewSeedSequencer(index: Index, *seeds, null_seed=True, limit=0, ctx=None, de
     return SeedSequencer(index, *seeds, null_seed=null_seed, limit=limit, ctx=ctx, device=device)
 
 
-def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
-    """dsx_assemble of a plan into the device tensor ``out``; ``store_bytes``
-    is the packed store buffer: host bytes (or a uint8 array), a device
-    tensor, or a ``(device pointer, length)`` pair (a DeviceStore's arena)."""
+def _assemble_args(plan, store_bytes, ctx, flags):
+    """-> (d_seeds, seed_lens, nseeds, store pointer, store length, flags, the
+    segment array, what must stay alive) for dsx_assemble and
+    dsx_assemble_inplace."""
     sq = plan.sequencer
-    ctx = ctx or sq.ctx
     ns = len(sq.seeds)
     used = set(np.unique(plan.segs["source"]).tolist())
     ptrs, lens = [], []
@@ -269,6 +278,7 @@ def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
         lens.append(ln)
     d_seeds = (ctypes.c_void_p * max(1, ns))(*ptrs)
     d_lens = (ctypes.c_uint64 * max(1, ns))(*lens)
+    keep = None
     if isinstance(store_bytes, tuple):
         sptr, slen, flags = int(store_bytes[0]), int(store_bytes[1]), flags | _lib.DSX_STORE_DEVICE
     elif _is_device(store_bytes):
@@ -279,14 +289,73 @@ def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
             else np.ascontiguousarray(store_bytes, dtype=np.uint8)
         sptr, slen = (keep.ctypes.data if keep.size else 0), keep.size
     segs = np.ascontiguousarray(plan.segs)
+    return d_seeds, d_lens, ns, sptr, slen, flags, segs, keep
+
+
+def assemble(plan: Plan, out, store_bytes=b"", ctx=None, flags=0):
+    """dsx_assemble of a plan into the device tensor ``out``; ``store_bytes``
+    is the packed store buffer: host bytes (or a uint8 array), a device
+    tensor, or a ``(device pointer, length)`` pair (a DeviceStore's arena)."""
+    ctx = ctx or plan.sequencer.ctx
+    d_seeds, d_lens, ns, sptr, slen, flags, segs, _alive = _assemble_args(plan, store_bytes, ctx, flags)
     _check(lib().dsx_assemble(ctx.h, ctypes.c_void_p(segs.ctypes.data), len(segs), d_seeds, d_lens, ns,
                               ctypes.c_void_p(sptr), slen, ctypes.c_void_p(out.data_ptr()),
                               out.numel() * out.element_size(), flags), ctx)
     return out
 
 
+def assemble_inplace(plan: Plan, out, have_len, keep=None, store_bytes=b"", ctx=None, flags=0,
+                     window=0, stash=0):
+    """dsx_assemble_inplace: the device tensor ``out`` holds ``have_len`` bytes
+    of old content and becomes the plan's target.  ``plan.segs`` may name
+    ``SRC_SELF`` (the buffer's own old content); ``keep`` is one byte per
+    target chunk, set where the chunk already lies at its place.  ``flags``
+    may force a direction (DSX_INPLACE_ASCENDING / DSX_INPLACE_DESCENDING).
+    Returns dsx_inplace_totals_t as a dict; a stash too small raises
+    :class:`StorageError` with ``.needed``, and the buffer is unchanged."""
+    sq = plan.sequencer
+    ctx = ctx or sq.ctx
+    d_seeds, d_lens, ns, sptr, slen, flags, segs, _alive = _assemble_args(plan, store_bytes, ctx, flags)
+    ends = np.ascontiguousarray(sq.ends, dtype=np.uint64)
+    kp = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8)
+    new_len = int(ends[-1]) if ends.size else 0
+    tot = _lib.InplaceTotals()
+    rc = lib().dsx_assemble_inplace(
+        ctx.h, ctypes.c_void_p(segs.ctypes.data if len(segs) else None), len(segs),
+        ctypes.c_void_p(ends.ctypes.data if ends.size else None), ends.size,
+        ctypes.c_void_p(kp.ctypes.data) if kp is not None and kp.size else None,
+        d_seeds, d_lens, ns, ctypes.c_void_p(sptr), slen, ctypes.c_void_p(out.data_ptr()),
+        out.numel() * out.element_size(), int(have_len), new_len, int(window), int(stash), flags,
+        ctypes.byref(tot))
+    totals = {k: getattr(tot, k) for k, _ in _lib.InplaceTotals._fields_ if k != "reserved"}
+    if rc == _lib.DSX_E_CAPACITY:
+        raise StorageError(totals["stash_peak"], totals)
+    _check(rc, ctx)
+    return totals
+
+
+def chunk_keep(ptr, have_len, ends, ids, ctx=None, algo=None):
+    """dsx_chunk_keep: which chunks of a target (``ends``, ``ids`` (n, 32)
+    uint8, both host arrays) already lie at their place in the device buffer
+    ``ptr[0:have_len]`` of unknown content -> a uint8 mask, one byte per chunk
+    (assemble.go:38-48).  A chunk reaching beyond ``have_len`` is not kept."""
+    from .make import _digest_code
+    ctx = ctx or _lib.default_context()
+    ends = np.ascontiguousarray(ends, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint8)
+    keep = np.zeros(ends.size, dtype=np.uint8)
+    kept = ctypes.c_uint64()
+    if ends.size:
+        _check(lib().dsx_chunk_keep(ctx.h, ctypes.c_void_p(ptr), int(have_len),
+                                    ctypes.c_void_p(ends.ctypes.data), ends.size,
+                                    ctypes.c_void_p(ids.ctypes.data), _digest_code(algo),
+                                    ctypes.c_void_p(keep.ctypes.data), ctypes.byref(kept), 0), ctx)
+        assert int(keep.sum()) == kept.value
+    return keep
+
+
 def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=None, device=0,
-                 validate=True):
+                 validate=True, out=None, have=None, window=0, stash=0):
     """AssembleFile (assemble.go:93-309) into HBM: returns ``(uint8 device
     tensor, ExtractStats dict)``.
 
@@ -314,11 +383,40 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
     packed buffer as the self seed would copy them), and
     ``bytes-copied-from-seeds`` their bytes.  ``seeds`` counts the null seed.
     ``chunks-in-place``, ``bytes-cloned-from-seeds`` and ``blocksize`` are 0.
+
+    In place (``extract -k``, assemble.go:29-49, :89-92): with ``out``, a uint8
+    device tensor of at least ``index.Length()`` bytes, the target is built
+    inside that buffer (dsx_assemble_inplace) and ``(out[:length], stats)``
+    returned; nothing of the target's size is allocated.  ``have`` says what
+    the buffer holds.  An :class:`Index`: the old version, ``out[:have.Length()]``.
+    It joins the sequencer as the first file seed (ties go to it), its segments
+    become moves inside the buffer, and a chunk with the same start, end and ID
+    in both indexes that the plan took from it is kept; Plan.Validate re-hashes
+    what the plan uses of it like any seed's, and if that fails the seed is
+    skipped and the call goes on as for an ``int``.  An ``int``: that many
+    bytes of unknown content (a resumed extract); dsx_chunk_keep hashes the
+    target's chunks where they would lie and keeps those that match, and there
+    is no self seed.  None: nothing usable.  ``window`` and ``stash`` are
+    dsx_assemble_inplace's (0: its defaults); a stash too small raises
+    :class:`StorageError` with ``.needed`` and leaves the buffer as it was.
+    Only chunks that are written are fetched from ``store`` or looked up in a
+    DeviceStore.  The read-back check hashes one span, from the first to the
+    last chunk not kept.  ``chunks-in-place`` counts the kept chunks,
+    ``chunks-from-store`` the distinct chunks fetched, ``chunks-from-seeds``
+    the rest, chunks moved inside the buffer included; ``stats["inplace"]``
+    holds dsx_inplace_totals_t.  Deviation: Go counts a chunk as in place only
+    on the store path (writeChunk); here a kept chunk is kept and counted
+    whatever the plan chose for it.
     """
     import torch
 
     ctx = ctx or _lib.default_context(device)
     seeds = list(seeds)
+    if out is not None:
+        return assemble_blob_inplace(index, store, seeds, null_seed, limit, ctx, validate, out, have,
+                                     window, stash)
+    if have is not None:
+        raise ValueError("have= describes out=")
     sq = SeedSequencer(index, *seeds, null_seed=null_seed, limit=limit, ctx=ctx)
     n = len(sq.ends)
     stats = {"chunks-from-seeds": 0, "chunks-from-store": 0, "chunks-in-place": 0,
@@ -379,3 +477,139 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
     stats["chunks-from-seeds"] = n - t["store_unique"]
     stats["bytes-copied-from-seeds"] = t["seed_bytes"] + t["null_bytes"] + t["store_bytes"] - t["store_len"]
     return out, stats
+
+
+def _same_chunks(ends, ids, old_ends, old_ids):
+    """One byte per target chunk: the old index has a chunk with the same
+    start, end and ID."""
+    n = len(ends)
+    keep = np.zeros(n, dtype=np.uint8)
+    if not n or not len(old_ends):
+        return keep
+    starts = np.concatenate([np.zeros(1, dtype=np.uint64), ends[:-1]])
+    old_starts = np.concatenate([np.zeros(1, dtype=np.uint64), old_ends[:-1]])
+    j = np.minimum(np.searchsorted(old_ends, ends), len(old_ends) - 1)
+    same = (old_ends[j] == ends) & (old_starts[j] == starts) & (ends > starts)
+    same &= np.all(old_ids[j] == ids, axis=1)
+    keep[same] = 1
+    return keep
+
+
+def assemble_blob_inplace(index, store, seeds, null_seed, limit, ctx, validate, out, have, window,
+                          stash, flags=0, trace=None):
+    """AssembleBlob(out=...): see there.  ``flags`` may force a direction
+    (DSX_INPLACE_ASCENDING / DSX_INPLACE_DESCENDING); ``trace`` (a dict)
+    receives what went into dsx_assemble_inplace: ``segs``, ``keep``,
+    ``have_len``."""
+    from .copy import Cache, Copy, _on_device
+    from .store import DeviceStore
+    if not _is_device(out) or out.element_size() != 1 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 device tensor")
+    cap = out.numel()
+    length = index.Length()
+    if cap < length:
+        raise ValueError(f"out holds {cap} bytes, the index needs {length}")
+    own = None
+    if isinstance(have, Index):
+        if have.Length() > cap:
+            raise ValueError("have is longer than out")
+        own = IndexSeed(have, (out.data_ptr(), have.Length()))
+        have_len = have.Length()
+    else:
+        have_len = int(have or 0)
+        if not 0 <= have_len <= cap:
+            raise ValueError("have is longer than out")
+    sq = SeedSequencer(index, *(([own] if own else []) + seeds), null_seed=null_seed, limit=limit, ctx=ctx)
+    n = len(sq.ends)
+    stats = {"chunks-from-seeds": 0, "chunks-from-store": 0, "chunks-in-place": 0,
+             "bytes-copied-from-seeds": 0, "bytes-cloned-from-seeds": 0, "blocksize": 0,
+             "bytes-total": length, "chunks-total": n, "seeds": len(seeds) + bool(null_seed)}
+    if n == 0:
+        return out[:0], stats
+    while True:
+        plan = sq.Plan()
+        if not validate:
+            break
+        try:
+            plan.Validate()
+            break
+        except SeedInvalid:
+            sq.Rewind()  # the seed is marked: the next plan does without it
+    segs = plan.segs.copy()
+    if own is not None and not own.IsInvalid():
+        mine = segs["source"] == 0
+        keep = _same_chunks(sq.ends, sq.ids, own.ends, own.ids)
+        if validate:  # only what Plan.Validate re-hashed is trusted to lie there
+            hashed = np.zeros(n, dtype=bool)
+            for f, c in zip(segs["first"][mine].tolist(), segs["count"][mine].tolist()):
+                hashed[f:f + c] = True
+            keep &= hashed
+        stats["seeds"] += 1
+    else:  # unknown content (or an old index that lied): ask the bytes themselves
+        mine = np.zeros(len(segs), dtype=bool)
+        keep = chunk_keep(out.data_ptr(), have_len, sq.ends, sq.ids, ctx=ctx)
+    if own is not None:  # number the sources without the self seed
+        src = segs["source"]
+        segs["source"] = np.where(mine, SRC_SELF, np.where(src > 0, src - 1, src))
+        own.close()
+    # a kept chunk is not written: nothing is fetched for it
+    st = (segs["source"] == SRC_STORE) & (keep[segs["first"]] != 0)
+    segs["source"][st] = SRC_NULL
+    segs["src_off"][st] = 0
+    sm = segs["source"] == SRC_STORE
+    sizes = np.diff(sq.ends, prepend=np.uint64(0))
+    raw = sq.ids.tobytes()
+    if trace is not None:
+        trace.update(segs=segs, keep=keep, have_len=have_len)
+    shim = SeedSequencer(index, *seeds, null_seed=null_seed, limit=limit, ctx=ctx)
+    if isinstance(store, Cache) and _on_device(store.s, store.l) and store.l.ctx is ctx:
+        Copy(sq.ids[np.unique(segs["first"][sm])], store.s, store.l)
+        store = store.l
+    if isinstance(store, DeviceStore) and store.ctx is ctx:
+        miss, wrong, bad = store.resolve(sq.ids, segs)
+        if miss or wrong:
+            cid = raw[32 * bad:32 * bad + 32]
+            if not store.HasChunk(cid):
+                raise ChunkMissing(cid)
+            raise ValueError(f"unexpected size for chunk {cid.hex()}")  # assemble.go:75-77
+        offs, at = np.unique(segs["src_off"][sm], return_index=True)  # (one arena offset a distinct chunk)
+        fetched, fetched_bytes = int(offs.size), int(sizes[segs["first"][sm][at]].sum())
+        with store._lock:
+            totals = assemble_inplace(Plan(shim, segs, None, None), out, have_len, keep, store.arena(),
+                                      ctx=ctx, flags=flags, window=window, stash=stash)
+    else:
+        # the packed buffer holds the chunks still needed, in the plan's order
+        chunks = plan.store_chunks
+        old_offs = np.cumsum(sizes[chunks], dtype=np.uint64) - sizes[chunks]
+        sel = np.isin(old_offs, segs["src_off"][sm])
+        new_offs = np.cumsum(sizes[chunks][sel], dtype=np.uint64) - sizes[chunks][sel]
+        segs["src_off"][sm] = new_offs[np.searchsorted(old_offs[sel], segs["src_off"][sm])]
+        parts = []
+        for i in chunks[sel].tolist():
+            cid = raw[32 * i:32 * i + 32]
+            data = store.GetChunk(cid)
+            if len(data) != int(sizes[i]):
+                raise ChunkInvalid(cid, digest.Digest.Sum(data))
+            parts.append(bytes(data))
+        fetched, fetched_bytes = int(sel.sum()), int(sizes[chunks][sel].sum())
+        totals = assemble_inplace(Plan(shim, segs, None, None), out, have_len, keep, b"".join(parts),
+                                  ctx=ctx, flags=flags, window=window, stash=stash)
+    if validate:
+        named = np.zeros(n, dtype=bool)
+        for f, c in zip(segs["first"].tolist(), segs["count"].tolist()):
+            named[f:f + c] = True
+        todo = np.flatnonzero((keep == 0) | ~named)
+        if todo.size:  # one span, from the first to the last chunk not kept
+            a, b = int(todo[0]), int(todo[-1]) + 1
+            got = chunk_ids(out.data_ptr(), length, sq.ends[a:b], int(sq.ends[a - 1]) if a else 0, ctx=ctx)
+            got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
+            bad = np.flatnonzero(np.any(got != sq.ids[a:b], axis=1))
+            if bad.size:
+                i = a + int(bad[0])
+                raise ChunkInvalid(raw[32 * i:32 * i + 32], got[i - a].tobytes())
+    stats["chunks-in-place"] = totals["kept_chunks"]
+    stats["chunks-from-store"] = fetched
+    stats["chunks-from-seeds"] = n - totals["kept_chunks"] - fetched
+    stats["bytes-copied-from-seeds"] = totals["written_bytes"] - fetched_bytes
+    stats["inplace"] = totals
+    return out[:length], stats

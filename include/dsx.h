@@ -668,6 +668,112 @@ int dsx_assemble(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
                  const void *store, uint64_t store_len, void *d_out, uint64_t out_len,
                  uint32_t flags);
 
+/* ---- updating a resident blob in place (assemble.go:29-49, :89-92, extract -k) --
+ * The buffer holds an old version (or anything) and becomes the target without
+ * a second buffer: chunks that already lie at their place are kept, old bytes
+ * that the target holds elsewhere are moved inside the buffer, the rest comes
+ * from seeds, the store and zeros.  DESIGN.md 4.6, "In place". */
+#define DSX_SRC_SELF (-3)   /* segment source: the buffer's own old content, src_off into it */
+#define DSX_SRC_STASH (-4)  /* in a schedule's tables only: the stash, src_off into it */
+#define DSX_INPLACE_ASCENDING 2048u  /* flag: visit the windows low to high */
+#define DSX_INPLACE_DESCENDING 4096u /* flag: visit them high to low (neither: the smaller stash) */
+#define DSX_INPLACE_SAVE 0u  /* launch kind A: buffer -> stash (dst_off is a stash offset) */
+#define DSX_INPLACE_WRITE 1u /* launch kind B: stash, buffer, seeds, store, zeros -> buffer */
+
+/* One launch of the gather kernel: the segments out_segs[seg0, seg0 + nsegs),
+ * ascending in dst_off, written into the stash (SAVE) or the buffer (WRITE);
+ * [lo, hi) spans their destinations.  A WRITE's destinations lie in window
+ * `window` of the buffer, a SAVE's SELF sources do. */
+typedef struct dsx_inplace_launch {
+    uint64_t window;
+    uint64_t seg0, nsegs;
+    uint64_t lo, hi;
+    uint32_t kind;
+    uint32_t reserved;
+} dsx_inplace_launch_t;
+
+typedef struct dsx_inplace_totals {
+    uint64_t windows;       /* windows that issued a launch */
+    uint64_t launches;      /* and how many (the needed launch_cap) */
+    uint64_t segments;      /* entries of all launch tables (the needed seg_cap) */
+    uint64_t kept_chunks, kept_bytes; /* chunks left where they lie */
+    uint64_t written_bytes; /* bytes the WRITE launches write */
+    uint64_t stash_bytes;   /* bytes that went through the stash */
+    uint64_t stash_peak;    /* the most the stash held at once: what stash_cap must allow */
+    uint32_t direction;     /* DSX_INPLACE_ASCENDING or DSX_INPLACE_DESCENDING: the one taken */
+    uint32_t reserved;
+} dsx_inplace_totals_t;
+
+/* The schedule of an in-place assembly.  Host code: no context, no GPU.
+ * segs[nsegs]: a plan as dsx_seed_plan returns it, ascending in dst_off, with
+ * DSX_SRC_SELF among the sources; ends[n]: the target's chunk ends (the first
+ * chunk starts at 0); keep[n] (may be NULL): one byte per chunk, set where the
+ * chunk already lies correct at its place; have_len: the old content's length;
+ * skew and tile: the gather's tile grid on the buffer (skew = the buffer's
+ * address modulo 16, tile = DSX_ASSEMBLE_TILE); window: a positive multiple of
+ * tile; flags: at most one of the two direction bits.
+ * Dropped: a SELF segment with src_off == dst_off and every chunk whose keep
+ * byte is set, whatever the plan chose for it (segments are cut at chunk
+ * boundaries by first / count).  Bytes nobody writes are never touched.  The
+ * rest is cut into windows of the buffer, byte x in window (x + skew) /
+ * window; a window with something to write issues a SAVE launch if old bytes
+ * of it are still needed, then a WRITE launch.  A launch never writes what it
+ * reads, reads only bytes no earlier launch has written, and a stash range is
+ * reused only after the last launch that reads it (dsx_inplace_plan.h has the
+ * invariant).  Without a forced direction the one with the smaller stash peak
+ * is taken, ascending on a tie.
+ * Returns DSX_E_CAPACITY with totals->stash_peak > stash_cap when the stash is
+ * too small (nothing is listed), or with totals->launches / ->segments the
+ * needed counts when launch_cap / seg_cap are.  Each old byte is saved at most
+ * once: stash_peak <= have_len.  Crafted arrays never index out of bounds;
+ * DSX_E_INVAL for segments that overlap, descend or exceed new_len, a SELF
+ * source beyond have_len, first + count > n, bytes or dst_off that are not
+ * those of the chunks named, ends that decrease or exceed new_len, a window
+ * that is no positive multiple of tile, skew >= tile, any other flag bit. */
+int dsx_inplace_plan(const dsx_plan_seg_t *segs, uint64_t nsegs, const uint64_t *ends, uint64_t n,
+                     const uint8_t *keep, uint64_t have_len, uint64_t new_len, uint64_t skew,
+                     uint64_t tile, uint64_t window, uint64_t stash_cap, uint32_t flags,
+                     dsx_inplace_launch_t *launches, uint64_t launch_cap,
+                     dsx_plan_seg_t *out_segs, uint64_t seg_cap, dsx_inplace_totals_t *totals);
+
+/* dsx_assemble into a buffer that holds the old version: d_buf[0, have_len) is
+ * the old content, d_buf[0, new_len) becomes the target, both within buf_cap.
+ * Runs dsx_inplace_plan with the buffer's skew and DSX_ASSEMBLE_TILE, uploads
+ * every launch table at once, takes the stash (stash_peak bytes) from the
+ * context's scratch (device_bytes) and enqueues the launches on the ctx stream
+ * with no host wait between them; one wait at the end.  window == 0: 128 MiB;
+ * stash_cap == 0: 2 x window.  Flags: DSX_STORE_DEVICE, DSX_ASSEMBLE_UNALIGNED
+ * and the direction bits.  totals may be NULL.
+ * Checked on the host before any launch, each DSX_E_INVAL with a
+ * dsx_last_error text naming the segment: dsx_assemble's checks with SELF a
+ * known source, dsx_inplace_plan's, new_len <= buf_cap, have_len <= buf_cap,
+ * no seed and no device store overlapping [d_buf, d_buf + buf_cap).
+ * DSX_E_CAPACITY: the stash is too small, totals->stash_peak says what it
+ * takes.  After any refusal the buffer is byte for byte what it was.  Not
+ * interruptible (as dsx_store_prune).  If a HIP call fails after the first
+ * WRITE launch the error is returned and dsx_last_error says that the buffer
+ * holds a partial update.  dsx_assemble itself keeps refusing SELF and an
+ * output that overlaps a source. */
+int dsx_assemble_inplace(dsx_ctx_t *ctx, const dsx_plan_seg_t *segs, uint64_t nsegs,
+                         const uint64_t *ends, uint64_t n, const uint8_t *keep,
+                         const void *const *d_seeds, const uint64_t *seed_lens, uint32_t nseeds,
+                         const void *store, uint64_t store_len, void *d_buf, uint64_t buf_cap,
+                         uint64_t have_len, uint64_t new_len, uint64_t window, uint64_t stash_cap,
+                         uint32_t flags, dsx_inplace_totals_t *totals);
+
+/* Which chunks of a target already lie at their place in a buffer of unknown
+ * content (assemble.go:38-48): the chunks [0, ends[0]), [ends[0], ends[1]), ...
+ * that lie wholly inside d_buf[0, have_len) are hashed where they lie (algo as
+ * dsx_chunk_ids) and compared with ids[n * 32]; keep[n] (host memory) receives
+ * one byte per chunk, 1 where the ID matches, and *n_kept their number.  A
+ * chunk reaching beyond have_len is not kept.  Only the n bytes come to the
+ * host.  flags: DSX_IDS_DEVICE, DSX_ENDS_DEVICE; any other bit DSX_E_INVAL.
+ * Host ends that decrease: DSX_E_INVAL.  n > 0xFFFFFFF0: DSX_E_INVAL.
+ * Synchronous. */
+int dsx_chunk_keep(dsx_ctx_t *ctx, const void *d_buf, uint64_t have_len, const uint64_t *ends,
+                   uint64_t n, const void *ids, int algo, uint8_t *keep, uint64_t *n_kept,
+                   uint32_t flags);
+
 /* ---- a chunk store in HBM: what lies between the write and the read side -------
  * The store desync puts between "which chunks are new" and "a plan plus the
  * chunks no seed holds" (store.go:21-33, local.go, chunkstorage.go), for blobs
