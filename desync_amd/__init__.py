@@ -21,6 +21,7 @@ mirror of the reference's Go API for that path:
     NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
     DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
     Copy, Cache, NewCache, DeviceStore.CopyFrom, Grow       (copy.go, cache.go)
+    NewIndexReadSeeker, IndexPos, Cat, read_ranges, DeviceIndex  (readseeker.go, cmd/desync/cat.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.
 """
@@ -38,6 +39,7 @@ from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Pl
     Segment, StorageError  # noqa: F401
 from .store import ChopBlob, ChopBlobs, DeviceStore  # noqa: F401
 from .copy import Cache, Copy, NewCache  # noqa: F401
+from .readseeker import Cat, DeviceIndex, IndexPos, NewIndexReadSeeker, read_ranges  # noqa: F401
 from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
     NewXChaCha20Poly1305, StoreOptions  # noqa: F401
 
@@ -52,5 +54,5 @@ __all__ = [
     "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing", "Copy", "Cache", "NewCache",
     "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
     "StoreOptions", "AuthenticationError", "IndexFromBlobs", "ChopBlobs", "cut_device_many",
-    "StorageError",
+    "StorageError", "NewIndexReadSeeker", "IndexPos", "Cat", "read_ranges", "DeviceIndex",
 ]

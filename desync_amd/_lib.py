@@ -63,7 +63,7 @@ EXPORTS = (
     "dsx_store_count", "dsx_store_put", "dsx_store_locate", "dsx_store_arena", "dsx_store_entries",
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
     "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305", "dsx_cut_device_many",
-    "dsx_inplace_plan", "dsx_assemble_inplace", "dsx_chunk_keep",
+    "dsx_inplace_plan", "dsx_assemble_inplace", "dsx_chunk_keep", "dsx_read_ranges", "dsx_read_plan",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -182,6 +182,28 @@ class StoreCopyTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("total", "copied", "copied_bytes", "present", "repeats", "missing", "first_missing",
                  "reserved")]
+
+
+class Range(ctypes.Structure):
+    """dsx_range_t: bytes [off, off + len) of the blob go to the output at dst_off."""
+
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("dst_off", ctypes.c_uint64)]
+
+
+class ReadTotals(ctypes.Structure):
+    """dsx_read_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("ranges", "bytes", "pieces", "store_bytes", "null_bytes", "missing", "wrong_size",
+                 "beyond")] + [("first_bad_range", ctypes.c_uint32),
+                               ("first_bad_chunk", ctypes.c_uint32)]
+
+
+class ReadPiece(ctypes.Structure):
+    """dsx_read_piece_t: one (range, chunk) pair of dsx_read_plan."""
+
+    _fields_ = [("chunk_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64),
+                ("bytes", ctypes.c_uint64), ("range", ctypes.c_uint32), ("chunk", ctypes.c_uint32)]
 
 
 class ManyOpts(ctypes.Structure):
@@ -377,6 +399,9 @@ def lib():
             "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
             "dsx_store_prune": (i32, [vp, vp, vp, u64, u64, P(StorePruneTotals), u32]),
             "dsx_store_copy": (i32, [vp, vp, vp, vp, u64, P(StoreCopyTotals), u32]),
+            "dsx_read_ranges": (i32, [vp, vp, vp, vp, u64, u64, vp, u64, vp, u64, vp, u64,
+                                      P(ReadTotals), u32]),
+            "dsx_read_plan": (i32, [vp, u64, u64, vp, u64, vp, u64, P(u64)]),
             "dsx_aead_seal": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, u32]),
             "dsx_aead_open": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64,
                                     P(u64), u32]),

@@ -44,6 +44,11 @@ struct StoreScratch {
   DevBuf<unsigned long long> pends;   // ... and their new ends (copied over the store's after the arena moved)
   DevBuf<uint8_t> bounce;             // prune: one window of the compacted arena
   DevBuf<uint32_t> srce;              // copy: the source store's entry number per ID
+  // dsx_read_ranges (dsx_read.hip): the staged ranges (3 words each), each range's first chunk,
+  // its table slots as a prefix sum inside its workgroup, the workgroups' sums, the counters,
+  // and the gather table (AsmSeg records)
+  DevBuf<unsigned long long> rd_ranges, rd_pref, rd_blk, rd_tot, rd_segs;
+  DevBuf<uint32_t> rd_first;
   std::vector<dsx_store*> live;       // the context's stores
 };
 

@@ -1,8 +1,8 @@
 // dsx_store.hip -- a chunk store in HBM (store.go:21-33, local.go,
 // chunkstorage.go): a deduplicating, tightly packed arena of chunk bytes keyed
 // by chunk ID, filled from a resident blob without a host round trip per
-// chunk, read in place by dsx_assemble and pruned in place (PruneStore.Prune,
-// local.go:163-202).  The counterpart of a LocalStore with Uncompressed: true
+// chunk, read in place by dsx_assemble and, range by range, by dsx_read_ranges
+// (dsx_read.hip), and pruned in place (PruneStore.Prune, local.go:163-202).  The counterpart of a LocalStore with Uncompressed: true
 // (store.go:98-99).
 //
 // Layout (dsx_store.h): entry e is the e-th chunk appended that no prune has
@@ -506,7 +506,9 @@ int stage_ids(dsx_ctx* c, const void* ids, uint64_t n, bool device, const uint8_
 uint64_t store_device_bytes(const dsx_ctx* c) {
   const StoreScratch& t = c->store;
   uint64_t b = t.flag.n + t.blk.n * 8 + t.tot.n * 8 + t.segs.n * 8 + t.offs.n * 8 + t.sizes.n * 8 +
-               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n + t.srce.n * 4;
+               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n + t.srce.n * 4 +
+               (t.rd_ranges.n + t.rd_pref.n + t.rd_blk.n + t.rd_tot.n + t.rd_segs.n) * 8 +
+               t.rd_first.n * 4;
   for (const dsx_store* s : t.live) b += s->ids.n + s->ends.n * 8 + s->slots.n * 4 + s->arena.n;
   return b;
 }
@@ -516,6 +518,8 @@ void store_release(dsx_ctx* c) {
   t.flag.release(), t.blk.release(), t.tot.release(), t.segs.release(), t.offs.release();
   t.sizes.release(), t.idx.release(), t.vids.release();
   t.pids.release(), t.pends.release(), t.bounce.release(), t.srce.release();
+  t.rd_ranges.release(), t.rd_pref.release(), t.rd_blk.release(), t.rd_tot.release();
+  t.rd_segs.release(), t.rd_first.release();
   for (dsx_store* s : t.live) free_store(s);
   t.live.clear();
 }

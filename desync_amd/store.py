@@ -16,7 +16,8 @@ on the GPU, keyed by chunk ID (dsx_store_*).  It is filled from a
 blob resident in HBM by kernels (``put``: which chunks are new, where they go
 and the copy, without a host round trip per chunk) and read in place by
 dsx_assemble (:func:`desync_amd.AssembleBlob` with such a store fetches
-nothing through the host).  ``Prune`` / ``RemoveChunk`` / ``Verify(repair=True)``
+nothing through the host; ``read_ranges`` reads byte ranges of an indexed blob
+out of it in one call, readseeker.py).  ``Prune`` / ``RemoveChunk`` / ``Verify(repair=True)``
 remove chunks and compact the arena where it lies (dsx_store_prune), giving
 the room back to later puts.  ``CopyFrom`` appends chunks of another store of the
 same context (dsx_store_copy; copy.py has ``Copy`` and ``Cache``), and ``Grow``
@@ -264,6 +265,15 @@ class DeviceStore:
                 _lib.check(lib().dsx_copy(self.ctx.h, out.ctypes.data,
                                           ctypes.c_void_p(base + int(offs[0])), size), self.ctx.h)
             return out.tobytes()
+
+    def read_ranges(self, index, ranges, out=None):
+        """:func:`desync_amd.read_ranges` of this store, under its lock: the byte
+        ranges ``ranges`` of the blob ``index`` (an :class:`Index` or a
+        :class:`DeviceIndex`) describes, in one dsx_read_ranges call
+        -> (device tensor, totals)."""
+        from .readseeker import read_ranges
+        with self._lock:
+            return read_ranges(index, self, ranges, out=out)
 
     def resolve(self, ids, segs, n=None):
         """dsx_store_resolve on a plan's structured segment array (in place)

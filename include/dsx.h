@@ -973,6 +973,88 @@ typedef struct dsx_store_copy_totals {
 int dsx_store_copy(dsx_ctx_t *ctx, dsx_store_t *dst, const dsx_store_t *src,
                    const void *ids, uint64_t n, dsx_store_copy_totals_t *totals, uint32_t flags);
 
+/* ---- byte ranges of an indexed blob, read out of a store ---------------------------
+ * What NewIndexReadSeeker / IndexPos.Read (readseeker.go), `desync cat -o -l`
+ * (cmd/desync/cat.go:95-105) and mount-index do one chunk at a time: the bytes
+ * [off, off + len) of the blob an index describes, taken from the chunks that
+ * hold them.  Here many ranges are one call, and neither the index, the
+ * store's offsets nor a segment list crosses to the host: DESIGN.md 4.10 has
+ * the launches.  The read-side counterpart of dsx_cut_device_many. */
+typedef struct dsx_range {
+    uint64_t off, len;  /* bytes [off, off + len) of the blob, in the coordinates of ends[]
+                           (chunk 0 begins at `start`) */
+    uint64_t dst_off;   /* ... go to d_out + dst_off */
+} dsx_range_t;          /* 24 bytes */
+
+typedef struct dsx_read_totals {
+    uint64_t ranges, bytes;  /* nranges, the sum of their lengths */
+    uint64_t pieces;         /* (range, chunk) pairs that share at least one byte */
+    uint64_t store_bytes, null_bytes; /* bytes of pieces served by the store / as zeros */
+    uint64_t missing;        /* pieces whose chunk the store lacks */
+    uint64_t wrong_size;     /* pieces whose stored size (null chunk: null_size) differs from the index's */
+    uint64_t beyond;         /* ranges with off < start or off + len > ends[n-1] */
+    uint32_t first_bad_range; /* lowest range with any of the three, else 0xFFFFFFFF */
+    uint32_t first_bad_chunk; /* lowest chunk position among the bad pieces, else 0xFFFFFFFF */
+} dsx_read_totals_t;         /* 72 bytes */
+
+typedef struct dsx_read_piece {
+    uint64_t chunk_off;  /* first byte of the piece inside its chunk */
+    uint64_t dst_off;    /* where it goes in the output */
+    uint64_t bytes;      /* > 0 */
+    uint32_t range, chunk; /* positions in ranges[] and in the index */
+} dsx_read_piece_t;      /* 32 bytes */
+
+/* ids[] holds the index's n 32-byte chunk IDs and ends[] its n cumulative chunk
+ * ends (host memory, or device memory with DSX_IDS_DEVICE / DSX_ENDS_DEVICE);
+ * chunk i is the blob's bytes [ends[i-1], ends[i]), ends[-1] = start.  ranges[]
+ * is host memory.  A range's bytes are written to d_out[dst_off, dst_off + len)
+ * (device memory of out_len bytes); bytes of d_out outside these windows are
+ * left untouched.
+ * Null chunk (readseeker.go:106-107): a chunk whose ID equals null_id is served
+ * as zeros without asking the store, whether or not the store holds it, and
+ * counts in null_bytes -- provided its size in the index equals null_size;
+ * otherwise it is a wrong_size (:123-126).  null_id == NULL: no null chunk.
+ * Every other chunk is looked up in the store: an absent one counts in missing
+ * (ChunkMissing, :109-112), one whose stored size differs from the index's in
+ * wrong_size ("unexpected size for chunk", :123-126).  A range with off < start
+ * or off + len > ends[n-1] (n == 0: > start) counts in beyond; clipping a read
+ * at the end of the blob (:157-170) is the caller's, who knows the length.
+ * All or nothing: with missing, wrong_size and beyond all zero the bytes are
+ * written; otherwise no byte of d_out is written.  Both return DSX_OK: the
+ * counts are the answer, as with dsx_store_resolve and dsx_store_copy.
+ * Ranges may overlap in the blob and repeat; a range of length 0 produces
+ * nothing; chunks of size 0 are no pieces and are not looked up.
+ * Refused with DSX_E_INVAL and a dsx_last_error text that names the range,
+ * before any device work: a NULL ctx (before HIP is touched), store or totals;
+ * an unknown flag bit; a missing array; nranges or n > 0xFFFFFFF0; dst_off +
+ * len > out_len; a dst_off below the one before it; destination windows that
+ * overlap; an output that overlaps the store's arena; host ends that decrease
+ * or begin below start; with host ends, more than 0xFFFFFFF0 (range, chunk)
+ * pairs (with device ends this is found after the first launch and nothing
+ * has been written).  A store of another context or a broken one: DSX_E_STATE.
+ * Device ends are trusted to ascend, as elsewhere; a list that does not makes
+ * the counts and the bytes meaningless but no kernel reads outside the index,
+ * the store or the ranges or writes outside the ranges' windows (DESIGN.md
+ * 4.10), and a chunk whose end lies below its start is a wrong_size.
+ * Synchronous on the ctx stream; the scratch counts in device_bytes.  Results
+ * are exact and the same on every run. */
+int dsx_read_ranges(dsx_ctx_t *ctx, const dsx_store_t *store,
+                    const void *ids, const uint64_t *ends, uint64_t start, uint64_t n,
+                    const uint8_t *null_id, uint64_t null_size,
+                    const dsx_range_t *ranges, uint64_t nranges,
+                    void *d_out, uint64_t out_len, dsx_read_totals_t *totals, uint32_t flags);
+
+/* The pieces dsx_read_ranges gathers, in order (by range, then by chunk), on the
+ * host and without a context (as dsx_plan_walk and dsx_inplace_plan): the same
+ * arithmetic the kernels run (dsx_read_geom.h).  ends[] is host memory.
+ * *npieces is always set to the number of pieces; with cap too small the first
+ * cap are written and the call returns DSX_E_CAPACITY.  DSX_E_INVAL: a missing
+ * array or npieces, ends that decrease or begin below start, a range beyond the
+ * blob. */
+int dsx_read_plan(const uint64_t *ends, uint64_t start, uint64_t n,
+                  const dsx_range_t *ranges, uint64_t nranges,
+                  dsx_read_piece_t *pieces, uint64_t cap, uint64_t *npieces);
+
 /* ---- the AEAD store converter: seal and open chunks in HBM -------------------------
  * What a store with `encryption: true` writes and reads (encrypt.go:84-101):
  * every chunk sealed on its own with XChaCha20-Poly1305 under one 256-bit key,
