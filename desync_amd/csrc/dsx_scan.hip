@@ -830,7 +830,7 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
   // Waves w and w + W/2 share a SIMD (waves are placed on the SIMDs
   // cyclically).  VALU issue favours the older wave, so left alone the
   // younger one finishes ~25 % later and the SIMD ends the scan with one wave
-  // (tools/scan_trace.py).  Each batch, the wave that has hashed fewer
+  // (tools/scan_trace.py).  Each trip, the wave that has hashed fewer
   // batches than its partner takes issue priority.
   const uint32_t partner = (wave + (uint32_t)W / 2u) % (uint32_t)W;
   uint32_t my_prog = 0;
@@ -1150,15 +1150,31 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
 
     // wait for batch b, copy this lane's row to registers, issue batch b+1
     // (or the next region's warm-up line) into the freed staging line
-    auto fetch = [&](uint32_t b) __attribute__((always_inline)) {
+    // What a line needs beyond that depends on where it stands, and the call
+    // site knows (site: 0 = line 0, 1 = line 1, 2 = the first line of a later
+    // trip, 3 = the other two lines of a trip), so the trip loop carries none
+    // of it at run time:
+    //  * the SIMD partner's progress is exchanged, and the issue priority set,
+    //    once per trip, at its first line (sites 1 and 2: a region's start
+    //    still balances at line 1); my_prog still counts lines.  Per line it
+    //    was 3 ds_write, 3 ds_read_b32, 3 v_readfirstlane, 3 compare-and-branch
+    //    pairs and 3 s_setprio per trip.
+    //  * the trace's wait stamp is taken at lines 0 and 1 only (sites 0 and 1).
+    //    Tested per line (b <= 1, which the compiler cannot rule out for
+    //    3t + 2: it wraps) it cost a v_cndmask, a v_cmp, 8 SALU and two
+    //    branches per line with no trace at all.
+    auto fetch = [&](uint32_t b, auto site) __attribute__((always_inline)) {
+      constexpr int kSite = decltype(site)::value;
+      constexpr bool kXchg = kSite == 1 || kSite == 2;
+      constexpr bool kEarly = kSite == 0 || kSite == 1;
       ++my_prog;
       uint32_t their = my_prog;
-      if constexpr (kBal) {
+      if constexpr (kBal && kXchg) {
         s_prog[wave] = my_prog;
         their = s_prog[partner];
       }
       uint64_t tw = 0;
-      const bool rs = a.trace && b <= 1u && nreg_done > 0;
+      const bool rs = kEarly && a.trace && b <= 1u && nreg_done > 0;
       if (VARIANT == 5 || rs) tw = __builtin_amdgcn_s_memtime();
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       uint64_t tw1 = 0;
@@ -1183,10 +1199,12 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
         tw2 = __builtin_amdgcn_s_memtime();
         copy_wait += tw2 - tw1;
       }
-      if (__builtin_amdgcn_readfirstlane(their) < my_prog)
-        __builtin_amdgcn_s_setprio(0);
-      else
-        __builtin_amdgcn_s_setprio(1);
+      if constexpr (kXchg) {
+        if (__builtin_amdgcn_readfirstlane(their) < my_prog)
+          __builtin_amdgcn_s_setprio(0);
+        else
+          __builtin_amdgcn_s_setprio(1);
+      }
       if (b + 1u < 3u * M + 1u) {
         issue(rsrc, sh, b + 1u);
       } else {
@@ -1203,7 +1221,7 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
       }
       if constexpr (VARIANT == 5) dma_issue += __builtin_amdgcn_s_memtime() - tw2;
     };
-    fetch(0u);
+    fetch(0u, std::integral_constant<int, 0>{});
     // warm-up: the last 48 bytes before the segment fill the window (no test)
     if constexpr (ROTF) {
       // positions -48 .. -1: nothing leaves the window yet (g ^= U), and the
@@ -1464,7 +1482,7 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
         }
       }
     };
-    fetch(1u);
+    fetch(1u, std::integral_constant<int, 1>{});
     {  // this segment's first 48 bytes, for the lane before (the handoff)
       uint8_t* const my_hand = s_hand + (wave * kWave + lane) * kHandoff;
 #pragma unroll
@@ -1484,19 +1502,21 @@ __global__ __launch_bounds__(W * kWave, W / 4) void scanl_kernel(ScanArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (VARIANT == 6) {
           if constexpr (gi < 48) {
-            if constexpr (gi % 16 == 0) fetch(3u * t + 1u + (uint32_t)(gi / 16));
+            if constexpr (gi % 16 == 0)
+              fetch(3u * t + 1u + (uint32_t)(gi / 16), std::integral_constant<int, 3>{});
           } else if constexpr (gi == 48) {
-            if (t + 1 < M) fetch(3u * t + 4u);
+            if (t + 1 < M) fetch(3u * t + 4u, std::integral_constant<int, 2>{});
           }
           __builtin_amdgcn_sched_barrier(0);
           compute_il(gc, std::integral_constant<int, gi % 48>{}, o0);
         } else {
           if constexpr (gi < 48) {
-            if constexpr (gi % 16 == 0) fetch(3u * t + 1u + (uint32_t)(gi / 16));
+            if constexpr (gi % 16 == 0)
+              fetch(3u * t + 1u + (uint32_t)(gi / 16), std::integral_constant<int, 3>{});
             issue_sub(std::integral_constant<int, gi>{});
           } else {
             if (t + 1 < M) {  // the next trip's first subgroups
-              if constexpr (gi == 48) fetch(3u * t + 4u);
+              if constexpr (gi == 48) fetch(3u * t + 4u, std::integral_constant<int, 2>{});
               issue_sub(std::integral_constant<int, gi - 48>{});
             }
           }
