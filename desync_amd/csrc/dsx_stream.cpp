@@ -265,15 +265,48 @@ int st_pump(dsx_ctx* c, bool sync) {
 
 // End of stream exactly at the last scanned byte: the chain's last chunk
 // ends there (no candidate after the carried cut, or it would have been
-// emitted: dsx_stitch.hip's undetermined-successor rule).
-void st_finish(dsx_ctx* c) {
+// emitted: dsx_stitch.hip's undetermined-successor rule).  With chunk IDs it
+// is hashed here, from the held bytes (st_room keeps them: the carried cut is
+// behind sched - st_halo), so that the ID queue stays as long as the cut
+// queue; nothing is on the GPU (the caller saw fly empty), slot 0 is free.
+int st_finish(dsx_ctx* c) {
   auto& s = c->st;
   if (s.carry < s.hend) {
+    if (s.ids >= 0) {
+      if (s.carry < s.hbase) {
+        c->err = "stream: the last chunk's bytes are not held";
+        return DSX_E_INTERNAL;
+      }
+      const uint64_t len = s.hend - s.carry;
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, grow(c, s.dbuf[0], len + 64));
+      HIPCHK(c, grow(c, s.dout[0], 1));
+      HIPCHK(c, grow(c, s.dids[0], 32));
+      HIPCHK(c, hipMemcpyAsync(s.dbuf[0].p, s.h + (s.carry - s.hbase), len, hipMemcpyHostToDevice,
+                               c->stream));
+      HIPCHK(c, hipMemcpyAsync(s.dout[0].p, &s.hend, sizeof(uint64_t), hipMemcpyHostToDevice,
+                               c->stream));
+      DigestArgs da{};
+      da.blob = s.dbuf[0].p;
+      da.base_off = s.carry;
+      da.len = len;
+      da.ends = s.dout[0].p;
+      da.first_start = s.carry;
+      da.n = 1;
+      da.ids = s.dids[0].p;
+      int rc = launch_digest(c, da, 1, s.ids);
+      if (rc) return rc;
+      std::array<uint8_t, 32> id;
+      HIPCHK(c, hipMemcpyAsync(id.data(), s.dids[0].p, 32, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      s.idq.push_back(id);
+    }
     s.cuts.push_back(s.hend);
     s.carry = s.hend;
   }
   s.final_pending = false;
   s.done = true;
+  return DSX_OK;
 }
 
 void st_restart(dsx_ctx* c, uint64_t at) {
@@ -436,7 +469,8 @@ extern "C" int dsx_stream_pop(dsx_ctx_t* c, uint64_t* start, uint64_t* size) {
       continue;
     }
     if (s.final_pending) {
-      st_finish(c);
+      int rc = st_finish(c);
+      if (rc) return rc;
       continue;
     }
     break;
@@ -596,10 +630,8 @@ extern "C" int dsx_stream_advance(dsx_ctx_t* c, uint64_t n) {
   // reader's; the chunker behaves as if the stream started at cur + n
   const uint64_t target = s.cur + n;
   s.last_chunk = nullptr;
-  if (target <= s.hend) {
-    s.skip = 0;
-  } else {
-    s.skip = target - s.hend;
+  if (target > s.hend) {  // (bytes still owed to an earlier Advance stay owed)
+    s.skip += target - s.hend;
     s.hbase = s.hend = target;  // nothing held
   }
   s.cur = target;

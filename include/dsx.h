@@ -255,7 +255,9 @@ const uint8_t *dsx_stream_chunk_data(dsx_ctx_t *ctx);
  * stream that overlaps the next batch.  Only before the first bytes of a
  * chain are scanned (else DSX_E_STATE).  dsx_stream_chunk_id returns the
  * 32-byte ID of the chunk the last pop returned (valid until the next call),
- * or NULL if it has none. */
+ * or NULL if it has none.  Every popped chunk of a chain with IDs has one, the
+ * last chunk of a stream whose bytes a DSX_STREAM_SYNC commit had all scanned
+ * before the end of input included; only the chunk of a flush has none. */
 int dsx_stream_ids(dsx_ctx_t *ctx, int algo);
 /* Up to cap confirmed chunks at once (a binding that hands out Next() results
  * without a call per chunk): the first starts at *start, chunk i ends at

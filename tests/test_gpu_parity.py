@@ -219,6 +219,118 @@ def test_chunker_advance(dctx):
     assert b == b""
 
 
+class _ShortReader:
+    """A reader whose calls return seeded lengths from 1 byte to 3 MiB (never
+    0 before the end), through read(n) or, with `into`, through readinto."""
+
+    def __init__(self, data, seed, into):
+        self.data, self.pos, self.rng, self.sizes = memoryview(data), 0, np.random.default_rng(seed), []
+        if into:
+            self.readinto = self._readinto
+        else:
+            self.read = self._read
+
+    def _take(self, room):
+        r = self.rng.random()
+        k = 1 if r < 0.2 else int(self.rng.integers(2, 5000)) if r < 0.5 else int(self.rng.integers(1, (3 << 20) + 1))
+        k = min(k, room, len(self.data) - self.pos)
+        self.pos += k
+        self.sizes.append(k)
+        return self.data[self.pos - k:self.pos]
+
+    def _read(self, n):
+        return bytes(self._take(n))
+
+    def _readinto(self, buf):
+        piece = self._take(len(buf))
+        buf[:len(piece)] = piece
+        return len(piece)
+
+
+@pytest.mark.parametrize("ids", [False, True])
+@pytest.mark.parametrize("into", [False, True])
+def test_chunker_short_reads(dctx, into, ids):
+    """Next() over a reader that returns 1 byte to 3 MiB per call: the
+    (start, bytes, ChunkID) sequence is the oracle's and hashlib's."""
+    import hashlib
+    import desync_amd
+    data = o.synth_uniform(41, 0, 12 << 20)
+    raw = data.tobytes()
+    reader = _ShortReader(raw, 5 + into, into)
+    c = desync_amd.NewChunker(reader, MIN, AVG, MAX, ctx=dctx)
+    try:
+        if ids:
+            c.EnableIDs("sha512-256")
+        start = 0
+        for end in o.chunk_stream(data, MIN, AVG, MAX).tolist():
+            s, b = c.Next()
+            assert (s, len(b)) == (start, end - start) and b == raw[start:end], (start, end)
+            if ids:
+                assert c.ChunkID() == hashlib.new("sha512_256", raw[start:end]).digest(), (start, end)
+            start = end
+        assert c.Next() == (len(raw), b"")
+    finally:
+        c.close()
+    # (12 MiB in calls of at most 3 MiB; what matters is that 1-byte and multi-MiB reads both occur)
+    assert reader.pos == len(raw) and reader.sizes.count(1) >= 2 and max(reader.sizes) > 2 << 20
+
+
+@pytest.mark.parametrize("ids", [False, True])
+def test_chunker_advance_random(dctx, ids):
+    """Seeded Advance(n) calls (n = 0, inside the next chunk, beyond the
+    reference's 10*max buffer and at times beyond every byte read so far)
+    after seeded numbers of Next() calls, two Advances in a row among them:
+    after each, the chunks are those of a stream that starts at cur + n
+    (chunker.go:292-309)."""
+    import hashlib
+    import desync_amd
+    mn, av, mx = 4096, 16384, 65536
+    data = o.synth_uniform(42, 0, 24 << 20)
+    raw = data.tobytes()
+    rng = np.random.default_rng(43 + ids)
+    c = desync_amd.NewChunker(_ShortReader(raw, 44, False), mn, av, mx, ctx=dctx)
+    try:
+        if ids:
+            c.EnableIDs("sha256")
+        cur, kinds, in_a_row, fresh = 0, set(), 0, False
+        ends = o.chunk_stream(data, mn, av, mx).tolist()
+        k = 0
+
+        def nexts(count):
+            nonlocal cur, k
+            for _ in range(count):
+                s, b = c.Next()
+                if k == len(ends):
+                    assert (s, b) == (cur, b""), (s, cur)
+                    return False
+                assert (s, len(b)) == (cur, ends[k] - cur) and b == raw[cur:ends[k]], (s, len(b), cur, ends[k])
+                if ids:
+                    assert c.ChunkID() == hashlib.sha256(b).digest(), cur
+                cur, k = ends[k], k + 1
+            return True
+
+        for _ in range(14):
+            count = int(rng.choice((0, 0, 1, 2, 5, 40)))
+            in_a_row += fresh and count == 0
+            if not nexts(count):
+                break
+            kind = str(rng.choice(("zero", "mid", "far", "farther")))
+            nxt = (ends[k] if k < len(ends) else cur) - cur
+            n = {"zero": 0, "mid": int(rng.integers(1, max(2, nxt))), "far": 10 * mx + int(rng.integers(1, 50000)),
+                 "farther": (9 << 20) + int(rng.integers(0, 1000))}[kind]
+            fresh = cur + n < len(raw)
+            if not fresh:
+                continue
+            kinds.add(kind)
+            c.Advance(n)
+            cur += n
+            ends, k = [cur + e for e in o.chunk_stream(data[cur:], mn, av, mx).tolist()], 0
+        assert kinds == {"zero", "mid", "far", "farther"} and in_a_row >= 1
+        assert nexts(len(ends) - k + 1) is False
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------- seeded random
 @pytest.mark.parametrize("seed,size", [(1, 1 << 20), (2, 3 * (1 << 20) + 12345), (3, 17 << 20),
                                        (4, 64 << 20)])
