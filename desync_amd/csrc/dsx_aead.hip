@@ -31,6 +31,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "dsx_callargs.h"
 #include "dsx_engine.h"
 
 namespace dsx {
@@ -513,16 +514,6 @@ void aead_release(dsx_ctx* c) {
 
 namespace {
 
-int aead_inval(dsx_ctx* c, const std::string& what) {
-  c->err = what;
-  return DSX_E_INVAL;
-}
-
-bool ranges_overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
-}
-
 // Clears what depends on the key.  Runs on every path out of a call that has
 // uploaded it, a failed one included.
 void aead_clear(dsx_ctx* c, uint64_t n, uint64_t slot_words) {
@@ -568,9 +559,9 @@ int aead_common_checks(dsx_ctx_t* c, int algo, const uint8_t* key, uint64_t n, u
                        uint32_t allowed) {
   if (!c || !key) return DSX_E_INVAL;
   c->err.clear();
-  if (algo != DSX_AEAD_XCHACHA20_POLY1305) return aead_inval(c, "unknown AEAD algorithm " + std::to_string(algo));
-  if (flags & ~allowed) return aead_inval(c, "unknown flag bit");
-  if (n > 0xFFFFFFF0ull) return aead_inval(c, "more than 0xFFFFFFF0 chunks");
+  if (algo != DSX_AEAD_XCHACHA20_POLY1305) return invalid(c, "unknown AEAD algorithm " + std::to_string(algo));
+  if (flags & ~allowed) return invalid(c, "unknown flag bit");
+  if (n > kCallMaxN) return invalid(c, "more than 0xFFFFFFF0 chunks");
   return DSX_OK;
 }
 
@@ -601,11 +592,11 @@ extern "C" int dsx_aead_seal(dsx_ctx_t* c, int algo, const uint8_t* key, const v
     uint64_t prev = start;
     for (uint64_t i = 0; i < n; ++i) {
       if (he[i] < prev)
-        return aead_inval(c, "chunk " + std::to_string(i) + ": its end is below " +
+        return invalid(c, "chunk " + std::to_string(i) + ": its end is below " +
                                  (i ? "the end before it" : "start"));
-      if (he[i] > src_len) return aead_inval(c, "chunk " + std::to_string(i) + ": its end is beyond the buffer");
+      if (he[i] > src_len) return invalid(c, "chunk " + std::to_string(i) + ": its end is beyond the buffer");
       if (he[i] - prev > kAeadMaxChunk)
-        return aead_inval(c, "chunk " + std::to_string(i) + ": more than 2^38 - 64 bytes");
+        return invalid(c, "chunk " + std::to_string(i) + ": more than 2^38 - 64 bytes");
       prev = he[i];
     }
     const uint64_t total = he[n - 1] - start;
@@ -614,8 +605,8 @@ extern "C" int dsx_aead_seal(dsx_ctx_t* c, int algo, const uint8_t* key, const v
       c->err = "the records take " + std::to_string(need) + " bytes";
       return DSX_E_CAPACITY;
     }
-    if (ranges_overlap((const uint8_t*)d_src + start, total, d_out, need))
-      return aead_inval(c, "the output overlaps the chunks");
+    if (overlaps((const uint8_t*)d_src + start, total, d_out, need))
+      return invalid(c, "the output overlaps the chunks");
 
     std::vector<uint8_t> drawn;
     if (!nonces) {  // crypto/rand.Read per chunk (encrypt.go:87)
@@ -694,13 +685,13 @@ extern "C" int dsx_aead_open(dsx_ctx_t* c, int algo, const uint8_t* key, const v
     uint64_t prev = start, total = 0;
     for (uint64_t i = 0; i < n; ++i) {
       if (rec_ends[i] < prev)
-        return aead_inval(c, "record " + std::to_string(i) + ": its end is below " +
+        return invalid(c, "record " + std::to_string(i) + ": its end is below " +
                                  (i ? "the end before it" : "start"));
-      if (rec_ends[i] > in_len) return aead_inval(c, "record " + std::to_string(i) + ": its end is beyond the buffer");
+      if (rec_ends[i] > in_len) return invalid(c, "record " + std::to_string(i) + ": its end is beyond the buffer");
       const uint64_t size = rec_ends[i] - prev;
       const uint64_t len = size >= kOverhead ? size - kOverhead : 0;
       if (len > kAeadMaxChunk)
-        return aead_inval(c, "record " + std::to_string(i) + ": more than 2^38 - 64 bytes of ciphertext");
+        return invalid(c, "record " + std::to_string(i) + ": more than 2^38 - 64 bytes of ciphertext");
       offs[i] = size >= kOverhead ? prev : kShort;
       total += len;
       pe[i] = total;
@@ -711,8 +702,8 @@ extern "C" int dsx_aead_open(dsx_ctx_t* c, int algo, const uint8_t* key, const v
       return DSX_E_CAPACITY;
     }
     if (total && !d_out) return DSX_E_INVAL;
-    if (ranges_overlap((const uint8_t*)d_in + start, rec_ends[n - 1] - start, d_out, total))
-      return aead_inval(c, "the output overlaps the records");
+    if (overlaps((const uint8_t*)d_in + start, rec_ends[n - 1] - start, d_out, total))
+      return invalid(c, "the output overlaps the records");
 
     AeadScratch& t = c->aead;
     hipStream_t st = c->stream;

@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "dsx_callargs.h"
 #include "dsx_engine.h"
 #include "dsx_inplace_plan.h"
 
@@ -154,12 +155,6 @@ namespace {
 int seg_error(dsx_ctx* c, uint64_t i, const char* what) {
   c->err = "segment " + std::to_string(i) + ": " + what;
   return DSX_E_INVAL;
-}
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
 }
 
 }  // namespace
@@ -446,7 +441,7 @@ extern "C" int dsx_chunk_keep(dsx_ctx_t* c, const void* d_buf, uint64_t have_len
   if ((n && (!ends || !ids || !keep)) || (have_len && !d_buf)) return DSX_E_INVAL;
   if (n_kept) *n_kept = 0;
   if (n == 0) return DSX_OK;
-  if (n > 0xFFFFFFF0ull) return DSX_E_INVAL;
+  if (n > kCallMaxN) return DSX_E_INVAL;
   c->err.clear();
   if (!(flags & DSX_ENDS_DEVICE)) {
     for (uint64_t i = 1; i < n; ++i)

@@ -347,16 +347,17 @@ struct dsx_ctx {
 };
 
 // Grow a device buffer; outstanding work may still use the old allocation, so
-// drain both streams before freeing it.  Allocates 25% headroom.
+// drain both streams before freeing it.  Allocates 25% headroom, or none for
+// a buffer whose size the call's arguments fix (prune's scratch).
 template <class T>
-inline hipError_t grow(dsx_ctx* c, DevBuf<T>& b, size_t n) {
+inline hipError_t grow(dsx_ctx* c, DevBuf<T>& b, size_t n, bool headroom = true) {
   if (b.p && b.n >= n) return hipSuccess;
   if (b.p) {
     (void)hipStreamSynchronize(c->stream);
     (void)hipStreamSynchronize(c->copy_stream);
     if (c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
   }
-  return b.ensure(n + n / 4 + 64);
+  return b.ensure(headroom ? n + n / 4 + 64 : n);
 }
 
 // The stream a piece's scan waits on for its input bytes (an H2D copy event,

@@ -28,6 +28,7 @@
 #include <atomic>
 #include <random>
 
+#include "dsx_callargs.h"
 #include "dsx_engine.h"
 #include "dsx_idset_dev.h"
 
@@ -163,10 +164,6 @@ int idset_enqueue_build(dsx_ctx* c, const uint8_t* d_ids, uint64_t n, uint32_t* 
 
 namespace {
 
-constexpr uint64_t kIdsetMaxN = 0xFFFFFFF0ull;
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 void free_set(dsx_idset* s) {
   s->ids.release();
   s->slots.release();
@@ -196,7 +193,7 @@ extern "C" int dsx_idset_create(dsx_ctx_t* c, const void* ids, uint64_t n, uint3
                                 dsx_idset_t** out) {
   DSX_FLUSH_BEHIND(c);
   const uint32_t known = DSX_IDS_DEVICE;
-  if (!c || !out || (n && !ids) || (flags & ~known) != 0 || n > kIdsetMaxN) return DSX_E_INVAL;
+  if (!c || !out || (n && !ids) || (flags & ~known) != 0 || n > kCallMaxN) return DSX_E_INVAL;
   *out = nullptr;
   HIPCHK(c, hipSetDevice(c->device));
   c->err.clear();
@@ -258,7 +255,7 @@ extern "C" int dsx_dedup(dsx_ctx_t* c, const void* ids, const uint64_t* ends, ui
   const uint32_t f_ids = DSX_IDS_DEVICE, f_ends = DSX_ENDS_DEVICE, f_out = DSX_OUT_DEVICE,
                  f_sizes = DSX_SIZES;
   if (!c || (flags & ~(f_ids | f_ends | f_out | f_sizes)) != 0) return DSX_E_INVAL;
-  if (n > kIdsetMaxN || (n && (!ids || !ends))) return DSX_E_INVAL;
+  if (n > kCallMaxN || (n && (!ids || !ends))) return DSX_E_INVAL;
   if (seed && seed->ctx != c) {
     c->err = "the seed set belongs to another context";
     return DSX_E_INVAL;
@@ -283,18 +280,11 @@ extern "C" int dsx_dedup(dsx_ctx_t* c, const void* ids, const uint64_t* ends, ui
 
   // arguments the kernels cannot read in place (host memory, or a device
   // pointer below the vector loads' alignment) are staged in the context
-  const uint8_t* d_ids = (const uint8_t*)ids;
-  if (!(flags & f_ids) || !aligned(ids, 16)) {
-    HIPCHK(c, grow(c, t.ids, n * 32));
-    HIPCHK(c, hipMemcpyAsync(t.ids.p, ids, n * 32, hipMemcpyDefault, st));
-    d_ids = t.ids.p;
-  }
-  const uint64_t* d_ends = ends;
-  if (!(flags & f_ends) || !aligned(ends, 8)) {
-    HIPCHK(c, grow(c, t.ends, n));
-    HIPCHK(c, hipMemcpyAsync(t.ends.p, ends, n * 8, hipMemcpyDefault, st));
-    d_ends = t.ends.p;
-  }
+  const uint8_t* d_ids = nullptr;
+  const uint64_t* d_ends = nullptr;
+  int rc = stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  if (!rc) rc = stage_ends(c, ends, n, (flags & f_ends) != 0, &d_ends);
+  if (rc) return rc;
   uint32_t* d_first = first_pos;
   if (first_pos && (!(flags & f_out) || !aligned(first_pos, 4))) {
     HIPCHK(c, grow(c, t.first_pos, n));
@@ -309,7 +299,7 @@ extern "C" int dsx_dedup(dsx_ctx_t* c, const void* ids, const uint64_t* ends, ui
   HIPCHK(c, grow(c, t.slots, cap));
   HIPCHK(c, grow(c, t.tot, kIdsetCounters));
   const uint64_t salt = idset_next_salt();
-  int rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
   if (rc) return rc;
   // (the insert left the distinct count in tot[0]; the probe counts it again
   // from first_pos, so start it from zero)
@@ -369,7 +359,7 @@ extern "C" int dsx_seed_plan(dsx_ctx_t* c, const void* ids, const uint64_t* ends
   DSX_FLUSH_BEHIND(c);
   const uint32_t f_ids = DSX_IDS_DEVICE, f_ends = DSX_ENDS_DEVICE;
   if (!c || !totals || (flags & ~(f_ids | f_ends)) != 0) return DSX_E_INVAL;
-  if (n > kIdsetMaxN || (n && (!ids || !ends))) return DSX_E_INVAL;
+  if (n > kCallMaxN || (n && (!ids || !ends))) return DSX_E_INVAL;
   if (nseeds && (!seeds || !seed_ends || !seed_counts)) return DSX_E_INVAL;
   *totals = dsx_plan_totals_t{};
   IdsetScratch& t = c->idset;

@@ -1,16 +1,17 @@
 // dsx_idset_dev.h -- the device side of the keyed open-addressing ID table,
 // shared by the translation units whose kernels probe one (dsx_idset.hip: the
 // sets; dsx_store.hip: the chunk store), and the host helpers that size, key
-// and build a table.  The table's properties are stated in dsx_idset.hip.
+// and build a table.  The table's properties are stated in dsx_idset.hip.  The
+// wave reductions the kernels count with are dsx_blockscan.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-struct dsx_ctx;
+#include "dsx_blockscan.h"
+#include "dsx_engine.h"
 
 namespace dsx {
 
-typedef unsigned long long u64;
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr int kIdsetThreads = 256;
 
@@ -47,12 +48,6 @@ __device__ __forceinline__ u64 hash_id(const Id32& a, u64 salt) {
   return mix64(h ^ ((u64)a.hi.w << 32 | a.hi.z));
 }
 
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;  // (lane 0 holds the wave's sum)
-}
-
 __device__ __forceinline__ uint32_t idset_find(const uint8_t* ids, u64 n, const uint32_t* slots,
                                                u64 mask, u64 salt, const Id32& key) {
   u64 s = hash_id(key, salt) & mask;
@@ -62,6 +57,29 @@ __device__ __forceinline__ uint32_t idset_find(const uint8_t* ids, u64 n, const 
     if (j < n && same_id(load_id(ids, j), key)) return j;
   }
   return kEmpty;
+}
+
+// the entry of `key` in a store (dsx_store.h), or kEmpty
+__device__ __forceinline__ uint32_t store_find(const StoreView& v, const Id32& key) {
+  return idset_find(v.ids, v.n, v.slots, v.mask, v.salt, key);
+}
+
+// Claims for `entry` the first empty slot on id's probe sequence.  For IDs
+// that differ from each other and from every ID the table holds: the IDs a put
+// or a copy appends in one call (that is what its select selected), and a
+// store's own entries claiming their slots in a cleared table.  No ID is
+// compared: a comparison would read an entry another lane of the same launch
+// is still writing.  No lane waits for another; the probe loop is bounded by
+// the capacity.
+__device__ __forceinline__ void idset_claim_empty(uint32_t* slots, u64 mask, u64 salt, const Id32& id,
+                                                  uint32_t entry) {
+  u64 s = hash_id(id, salt) & mask;
+  for (u64 step = 0; step <= mask; ++step, s = (s + 1) & mask) {
+    uint32_t cur = __hip_atomic_load(&slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur != kEmpty) continue;
+    cur = atomicCAS(&slots[s], kEmpty, entry);
+    if (cur == kEmpty) break;
+  }
 }
 
 // One lane per ID.  *claimed counts the slots taken: the distinct IDs.

@@ -14,10 +14,12 @@
 //                       chain walked by one wave (rel_step of dsx_chain.h with
 //                       L = B1, entry B0).  Blob i's cuts go to its own slots
 //                       of the staging list, their count to cnt[i].
-//   many_scan_kernel    exclusive scan of cnt[] over the blobs: blob_first.
+//   many_scan_kernel    exclusive scan of cnt[] over the blobs (block_scan,
+//                       dsx_blockscan.h): blob_first.
 //   many_gather_kernel  staging list -> contiguous cut list.
 #include <hip/hip_runtime.h>
 
+#include "dsx_blockscan.h"
 #include "dsx_chain.h"
 #include "dsx_common.h"
 #include "dsx_many.h"
@@ -158,37 +160,21 @@ __global__ __launch_bounds__(kManyWalkThreads) void many_walk_kernel(ManyWalkArg
 // res[0] the total, res[1] the flagged blobs.
 __global__ __launch_bounds__(kManyScanThreads) void many_scan_kernel(ManyFinishArgs a) {
   constexpr int NT = kManyScanThreads;
-  __shared__ uint64_t s_wave[NT / 64];
   __shared__ unsigned long long s_flag;
   const ManyBlobs& mb = a.mb;
-  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (threadIdx.x == 0) s_flag = 0;
   uint64_t base = 0, nflag = 0;
   for (uint64_t b = 0; b < mb.nblobs; b += NT) {
     const uint64_t i = b + threadIdx.x;
-    uint64_t v = 0;
+    u64 v[1] = {0}, before[1], all[1];
     if (i < mb.nblobs) {
-      v = mb.cnt[i];
+      v[0] = mb.cnt[i];
       nflag += mb.flag[i] ? 1u : 0u;
     }
-    uint64_t incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t t = __shfl_up((unsigned long long)incl, (unsigned)d, 64);
-      if (lane >= (uint32_t)d) incl += t;
-    }
-    if (lane == 63) s_wave[wv] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-      const uint64_t t = s_wave[w];
-      before += (w < (int)wv) ? t : 0ull;
-      all += t;
-    }
-    __syncthreads();
-    if (i < mb.nblobs) a.first[i] = base + before + incl - v;
-    base += all;
+    block_scan<NT, 1>(v, before, all);
+    if (i < mb.nblobs) a.first[i] = base + before[0];
+    base += all[0];
+    __syncthreads();  // (the next pass writes the wave totals again)
   }
   if (nflag) atomicAdd(&s_flag, (unsigned long long)nflag);
   __syncthreads();

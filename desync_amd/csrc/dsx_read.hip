@@ -10,7 +10,7 @@
 //           (one per chunk from the first to the last) as a prefix sum inside
 //           its workgroup, and whether it leaves the blob;
 //   scan    one workgroup turns the workgroups' sums into exclusive prefix sums
-//           and leaves the total (the store's block-scan pattern), so range r's
+//           and leaves the total (the store's scan, dsx_blockscan.h), so range r's
 //           slots are a contiguous, ascending slice of the table;
 //   emit    work is divided by slots, not by ranges: a lane finds its slot's
 //           range by bisection over the prefix sums, its chunk from the range's
@@ -34,6 +34,7 @@
 #include <string>
 #include <vector>
 
+#include "dsx_callargs.h"
 #include "dsx_engine.h"
 #include "dsx_idset_dev.h"
 #include "dsx_read_geom.h"
@@ -41,7 +42,6 @@
 namespace dsx {
 
 constexpr int kReadThreads = 256;
-constexpr int kReadWaves = kReadThreads / 64;
 constexpr u64 kNone = ~0ull;
 
 // the counters of a call (rd_tot)
@@ -67,11 +67,7 @@ struct ReadArgs {
   u64 start, n;
   Id32 null_id;
   u64 has_null, null_size;
-  const uint8_t* st_ids;  // the store
-  const uint64_t* st_ends;
-  const uint32_t* st_slots;
-  u64 st_n, st_mask, st_salt, st_bytes;
-  const uint8_t* arena;
+  StoreView st;     // the store (only read)
   u64* pref;        // [nranges] slots of the ranges before r in r's workgroup
   uint32_t* first;  // [nranges] the first chunk of range r
   u64* blk;         // [workgroups of the count] their slots, then the exclusive prefix sums
@@ -81,27 +77,9 @@ struct ReadArgs {
   u64 cap;  // records segs[] holds
 };
 
-__device__ __forceinline__ u64 read_wave_scan(u64 v) {  // inclusive, over the wave's lanes
-  const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 t = __shfl_up(v, o, 64);
-    if (lane >= (uint32_t)o) v += t;
-  }
-  return v;
-}
-
-__device__ __forceinline__ u64 wave_min(u64 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v = std::min<u64>(v, __shfl_down(v, o, 64));
-  return v;  // (lane 0 holds the wave's minimum)
-}
-
 // One lane per range.
 __global__ __launch_bounds__(kReadThreads) void read_count_kernel(ReadArgs a) {
-  __shared__ u64 w_cnt[kReadWaves];
   const u64 r = (u64)blockIdx.x * kReadThreads + threadIdx.x;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   u64 cnt = 0;
   bool beyond = false;
   if (r < a.nranges) {
@@ -111,46 +89,15 @@ __global__ __launch_bounds__(kReadThreads) void read_count_kernel(ReadArgs a) {
     cnt = s.count;
     a.first[r] = (uint32_t)s.first;
   }
-  const u64 ic = read_wave_scan(cnt);
-  if (lane == 63) w_cnt[wave] = ic;
   const u64 bb = __ballot(beyond);
-  if (lane == 0 && bb) {
+  if ((threadIdx.x & 63) == 0 && bb) {
     atomicAdd(&a.tot[kRdBeyond], (u64)__popcll(bb));
     atomicMin(&a.tot[kRdBadRange], r + (u64)__ffsll((unsigned long long)bb) - 1);
   }
-  __syncthreads();
-  u64 off = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kReadWaves; ++w) {
-    if ((uint32_t)w < wave) off += w_cnt[w];
-    all += w_cnt[w];
-  }
-  if (r < a.nranges) a.pref[r] = off + ic - cnt;
-  if (threadIdx.x == 0) a.blk[blockIdx.x] = all;
-}
-
-// One workgroup: blk[] becomes its exclusive prefix sums, tot[kRdSlots] the total.
-__global__ __launch_bounds__(kReadThreads) void read_scan_kernel(u64* blk, u64 nblk, u64* tot) {
-  __shared__ u64 w_cnt[kReadWaves];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  u64 carry = 0;
-  for (u64 base = 0; base < nblk; base += kReadThreads) {
-    const u64 j = base + threadIdx.x;
-    const u64 c = j < nblk ? blk[j] : 0;
-    const u64 ic = read_wave_scan(c);
-    if (lane == 63) w_cnt[wave] = ic;
-    __syncthreads();
-    u64 off = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kReadWaves; ++w) {
-      if ((uint32_t)w < wave) off += w_cnt[w];
-      all += w_cnt[w];
-    }
-    if (j < nblk) blk[j] = carry + off + ic - c;
-    carry += all;
-    __syncthreads();  // (the next pass writes the wave totals again)
-  }
-  if (threadIdx.x == 0) tot[kRdSlots] = carry;
+  u64 before[1], all[1];
+  block_scan<kReadThreads, 1>({cnt}, before, all);
+  if (r < a.nranges) a.pref[r] = before[0];
+  if (threadIdx.x == 0) a.blk[blockIdx.x] = all[0];
 }
 
 // the slots in front of range m
@@ -200,15 +147,15 @@ __global__ __launch_bounds__(kReadThreads) void read_emit_kernel(ReadArgs a) {
             wrong = size != a.null_size;
             if (!wrong) g.bytes = p.bytes, from_null = p.bytes;
           } else {
-            const uint32_t e = idset_find(a.st_ids, a.st_n, a.st_slots, a.st_mask, a.st_salt, key);
+            const uint32_t e = store_find(a.st, key);
             miss = e == kEmpty;
             if (!miss) {
-              const u64 lo = e ? a.st_ends[e - 1] : 0, hi = a.st_ends[e];
-              // (hi <= st_bytes in a store the library filled: no record points outside the arena)
-              wrong = hi < lo || hi - lo != size || hi > a.st_bytes;
+              const u64 lo = e ? a.st.ends[e - 1] : 0, hi = a.st.ends[e];
+              // (hi <= st.bytes in a store the library filled: no record points outside the arena)
+              wrong = hi < lo || hi - lo != size || hi > a.st.bytes;
               if (!wrong) {
                 g.bytes = p.bytes, from_store = p.bytes;
-                g.src = a.arena + lo + p.chunk_off;
+                g.src = a.st.arena + lo + p.chunk_off;
               }
             }
           }
@@ -243,23 +190,8 @@ using namespace dsx;
 
 namespace {
 
-constexpr uint64_t kReadMaxN = 0xFFFFFFF0ull;  // the store's call limit
-
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-int invalid(dsx_ctx* c, const std::string& what) {
-  c->err = what;
-  return DSX_E_INVAL;
-}
-
 int range_error(dsx_ctx* c, uint64_t r, const char* what) {
   return invalid(c, "range " + std::to_string(r) + ": " + what);
-}
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
 }
 
 bool ends_ascend(const uint64_t* ends, uint64_t start, uint64_t n) {
@@ -279,7 +211,7 @@ extern "C" int dsx_read_plan(const uint64_t* ends, uint64_t start, uint64_t n,
   if (!npieces) return DSX_E_INVAL;
   *npieces = 0;
   if ((n && !ends) || (nranges && !ranges) || (cap && !pieces)) return DSX_E_INVAL;
-  if (n > kReadMaxN || nranges > kReadMaxN) return DSX_E_INVAL;
+  if (n > kCallMaxN || nranges > kCallMaxN) return DSX_E_INVAL;
   if (!ends_ascend(ends, start, n)) return DSX_E_INVAL;
   uint64_t k = 0;
   for (uint64_t r = 0; r < nranges; ++r) {
@@ -318,17 +250,10 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
   totals->first_bad_range = totals->first_bad_chunk = 0xFFFFFFFFu;
   // ---- every check comes before any device work ----------------------------------
   if ((flags & ~(f_ids | f_ends)) != 0) return invalid(c, "unknown flag bit");
-  const auto& live = c->store.live;
-  if (std::find(live.begin(), live.end(), s) == live.end()) {
-    c->err = "the store belongs to another context";
-    return DSX_E_STATE;
-  }
-  if (s->broken) {
-    c->err = "the store is broken: a prune failed while it moved the arena; destroy it";
-    return DSX_E_STATE;
-  }
-  if (nranges > kReadMaxN) return invalid(c, "more ranges than a call takes (0xFFFFFFF0)");
-  if (n > kReadMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_STATE);
+  if (s->broken) return broken_store(c);
+  if (nranges > kCallMaxN) return invalid(c, "more ranges than a call takes (0xFFFFFFF0)");
+  if (n > kCallMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
   if ((n && (!ids || !ends)) || (nranges && !ranges) || (out_len && !d_out))
     return invalid(c, "the IDs, the chunk ends, the ranges or the output are missing");
   if (out_len > UINT64_MAX - (uintptr_t)d_out) return invalid(c, "the output wraps the address space");
@@ -358,7 +283,7 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
     slots = 0;
     for (uint64_t r = 0; r < nranges; ++r) {
       slots += dsx_read::span_of(ends, start, n, ranges[r].off, ranges[r].len).count;
-      if (slots > kReadMaxN)
+      if (slots > kCallMaxN)
         return range_error(c, r, "more (range, chunk) pairs than a call takes (0xFFFFFFF0)");
     }
   }
@@ -368,23 +293,16 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
 
   HIPCHK(c, hipSetDevice(c->device));
   c->err.clear();
-  IdsetScratch& t = c->idset;
   StoreScratch& w = c->store;
   hipStream_t st = c->stream;
   // ---- stage ---------------------------------------------------------------------
   static_assert(sizeof(dsx_range_t) == 24, "three words a range (StoreScratch::rd_ranges)");
-  const uint8_t* d_ids = (const uint8_t*)ids;
-  if (n && (!(flags & f_ids) || !aligned(ids, 16))) {
-    HIPCHK(c, grow(c, t.ids, n * 32));
-    HIPCHK(c, hipMemcpyAsync(t.ids.p, ids, n * 32, hipMemcpyDefault, st));
-    d_ids = t.ids.p;
-  }
-  const uint64_t* d_ends = ends;
-  if (n && (!(flags & f_ends) || !aligned(ends, 8))) {
-    HIPCHK(c, grow(c, t.ends, n));
-    HIPCHK(c, hipMemcpyAsync(t.ends.p, ends, n * 8, hipMemcpyDefault, st));
-    d_ends = t.ends.p;
-  }
+  ReadArgs a{};
+  a.ids = (const uint8_t*)ids;  // (an index without chunks: nothing is staged, nothing reads them)
+  a.ends = ends;
+  int rc = n ? stage_ids(c, ids, n, (flags & f_ids) != 0, &a.ids) : DSX_OK;
+  if (!rc && n) rc = stage_ends(c, ends, n, (flags & f_ends) != 0, &a.ends);
+  if (rc) return rc;
   const uint64_t nblk = (nranges + kReadThreads - 1) / kReadThreads;
   HIPCHK(c, grow(c, w.rd_ranges, 3 * nranges));
   HIPCHK(c, grow(c, w.rd_pref, nranges));
@@ -397,11 +315,8 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
   HIPCHK(c, hipMemsetAsync(w.rd_tot.p, 0, kRdCounters * sizeof(u64), st));
   HIPCHK(c, hipMemsetAsync(w.rd_tot.p + kRdBadRange, 0xFF, 2 * sizeof(u64), st));  // none
 
-  ReadArgs a{};
   a.ranges = w.rd_ranges.p;
   a.nranges = nranges;
-  a.ids = d_ids;
-  a.ends = d_ends;
   a.start = start;
   a.n = n;
   if (null_id) {
@@ -409,14 +324,7 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
     a.has_null = 1;
     a.null_size = null_size;
   }
-  a.st_ids = s->ids.p;
-  a.st_ends = s->ends.p;
-  a.st_slots = s->slots.p;
-  a.st_n = s->chunks;
-  a.st_mask = s->cap - 1;
-  a.st_salt = s->salt;
-  a.st_bytes = s->bytes;
-  a.arena = s->arena.p;
+  a.st = view_of(s);
   a.pref = w.rd_pref.p;
   a.first = w.rd_first.p;
   a.blk = w.rd_blk.p;
@@ -425,8 +333,8 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
   // ---- count, scan, emit -----------------------------------------------------------
   hipLaunchKernelGGL(read_count_kernel, dim3((uint32_t)nblk), dim3(kReadThreads), 0, st, a);
   HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(read_scan_kernel, dim3(1), dim3(kReadThreads), 0, st, w.rd_blk.p, (u64)nblk,
-                     w.rd_tot.p);
+  hipLaunchKernelGGL(block_array_scan_kernel<1>, dim3(1), dim3(kArrayScanThreads), 0, st, w.rd_blk.p,
+                     (u64)nblk, w.rd_tot.p + kRdSlots);
   HIPCHK(c, hipGetLastError());
   // The emit's grid: enough workgroups for the slots the table can hold, at most
   // 8 a CU; the lanes stride over the rest.
@@ -446,7 +354,7 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
       c->err = "the gather table did not grow";
       return DSX_E_INTERNAL;
     }
-    if (tot[kRdSlots] > kReadMaxN)
+    if (tot[kRdSlots] > kCallMaxN)
       return invalid(c, "more (range, chunk) pairs than a call takes (0xFFFFFFF0)");
     HIPCHK(c, grow(c, w.rd_segs, 3 * tot[kRdSlots]));
     HIPCHK(c, hipMemsetAsync(w.rd_tot.p + kRdOverflow, 0, sizeof(u64), st));
@@ -461,7 +369,7 @@ extern "C" int dsx_read_ranges(dsx_ctx_t* c, const dsx_store_t* s, const void* i
   totals->first_bad_chunk = tot[kRdBadChunk] == kNone ? 0xFFFFFFFFu : (uint32_t)tot[kRdBadChunk];
   if (tot[kRdMissing] || tot[kRdWrong] || tot[kRdBeyond]) return DSX_OK;  // (the counts are the answer)
   // ---- gather ------------------------------------------------------------------------
-  const int rc = assemble_launch(c, a.segs, tot[kRdSlots], d_out, out_len, out_lo, out_hi, false);
+  rc = assemble_launch(c, a.segs, tot[kRdSlots], d_out, out_len, out_lo, out_hi, false);
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(st));
   return DSX_OK;

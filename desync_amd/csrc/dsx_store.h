@@ -30,6 +30,23 @@ struct dsx_store {
   bool broken = false;
 };
 
+// What a kernel takes of a store, by value in its arguments: n entries, bytes
+// of the arena used, mask = cap - 1.  The destination of a put or a copy is
+// written through its view, so the pointers are not const; the kernels that
+// only read a store take the same view.  Device side: store_find
+// (dsx_idset_dev.h).
+struct StoreView {
+  uint8_t* ids;
+  uint64_t* ends;
+  uint32_t* slots;
+  uint64_t n, mask, salt, bytes;
+  uint8_t* arena;
+};
+
+inline StoreView view_of(const dsx_store* s) {
+  return StoreView{s->ids.p, s->ends.p, s->slots.p, s->chunks, s->cap - 1, s->salt, s->bytes, s->arena.p};
+}
+
 // The scratch of the store's calls.  Grows once, reused.  (The call's own ID
 // table and the staged copies of host arguments are IdsetScratch's.)
 struct StoreScratch {

@@ -20,16 +20,15 @@
 //   scan    one workgroup turns those pairs into exclusive prefix sums;
 //   (the host reads the totals and the error word, and accepts the capacity)
 //   append  each new chunk takes entry chunks + rank and arena offset bytes +
-//           prefix (its rank inside the workgroup by ballot and popcount, its
-//           byte offset by wave shuffles and LDS), writes its ID, its end and
-//           a gather record, and claims a table slot;
+//           prefix (its rank and its byte offset inside the workgroup by
+//           block_scan, dsx_blockscan.h), writes its ID, its end and a gather
+//           record, and claims a table slot;
 //   copy    assemble_kernel over the gather records into arena[used, used +
 //           stored_bytes): tiles are cut over the destination.
 // The IDs appended in one call differ from each other and from every ID the
 // store holds (that is what select selected).  The insert therefore claims
-// the first empty slot on its probe sequence and compares no ID: a comparison
-// would read an entry another lane of the same launch is still writing.
-// No lane waits for another; the probe loops are bounded by the capacity.
+// the first empty slot on its probe sequence and compares no ID
+// (idset_claim_empty, dsx_idset_dev.h, has why).
 //
 // A prune is the put turned around (DESIGN.md 4.7 has the safety argument):
 //   mark     the call's own table over ids[], then one lane per entry: keep[e],
@@ -76,54 +75,36 @@
 #include <string>
 #include <vector>
 
+#include "dsx_callargs.h"
 #include "dsx_engine.h"
 #include "dsx_idset_dev.h"
 
 namespace dsx {
 
 constexpr int kStoreThreads = 256;
-constexpr int kStoreWaves = kStoreThreads / 64;
 
 struct PutArgs {
-  const uint8_t* ids;    // the call's IDs
-  const uint64_t* ends;  // chunk ends
+  const uint8_t* ids;  // the call's IDs
+  // a put's blob: its chunk ends, where chunk 0 starts, its length
+  const uint64_t* ends;
   u64 start, n, len;
   const uint8_t* blob;
   const uint32_t* slots;  // the call's own table (built by the launch before)
   u64 mask, salt;
-  uint8_t* st_ids;  // the store
-  uint64_t* st_ends;
-  uint32_t* st_slots;
-  u64 st_n, st_mask, st_salt, st_bytes;
-  uint8_t* flag;  // new[i]
-  u64* blk;       // {chunks, bytes} per workgroup
-  u64* tot;       // [kStoreCounters]
-  AsmSeg* segs;   // [n_new], written by the append
-  u64 n_new;      // the accepted total: the append's ranks stay below it
-  // a copy between stores: ends, len and blob are the source store's ends, used
-  // bytes and arena; start is unused
-  const uint8_t* src_ids;     // the source store's IDs ...
-  const uint32_t* src_slots;  // ... and its table; null with all
-  u64 src_n, src_mask, src_salt;
-  u64 all;         // DSX_COPY_ALL: ids is src_ids, ID i is entry i, no table of the call's
+  StoreView dst;   // the store the chunks go to
+  uint8_t* flag;   // new[i]
+  u64* blk;        // {chunks, bytes} per workgroup
+  u64* tot;        // [kStoreCounters]
+  AsmSeg* segs;    // [n_new], written by the append
+  u64 n_new;       // the accepted total: the append's ranks stay below it
+  StoreView src;   // a copy between stores: the store they come from, in place of the blob
+  u64 all;         // DSX_COPY_ALL: ids is src.ids, ID i is entry i, no table of the call's, src's not probed
   uint32_t* srce;  // [n] the source entry of ID i (written where flag[i] is set)
 };
-
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ u64 wave_scan(u64 v) {
-  const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u64 t = __shfl_up(v, o, 64);
-    if (lane >= (uint32_t)o) v += t;
-  }
-  return v;
-}
 
 // One lane per chunk.  A chunk whose end lies below its start or beyond the
 // blob sets the error word (the host then stops before the append).
 __global__ __launch_bounds__(kStoreThreads) void store_select_kernel(PutArgs a) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
   bool is_new = false, present = false, bad = false;
   u64 size = 0;
@@ -132,7 +113,7 @@ __global__ __launch_bounds__(kStoreThreads) void store_select_kernel(PutArgs a) 
     bad = e < prev || e > a.len;
     const Id32 me = load_id(a.ids, i);
     if (idset_find(a.ids, a.n, a.slots, a.mask, a.salt, me) == (uint32_t)i) {
-      present = idset_find(a.st_ids, a.st_n, a.st_slots, a.st_mask, a.st_salt, me) != kEmpty;
+      present = store_find(a.dst, me) != kEmpty;
       is_new = !present;
     }
     if (is_new && !bad) size = e - prev;
@@ -140,52 +121,40 @@ __global__ __launch_bounds__(kStoreThreads) void store_select_kernel(PutArgs a) 
   }
   const u64 bn = __ballot(is_new), bp = __ballot(present), bb = __ballot(bad);
   const u64 bytes = wave_sum(size);
-  const uint32_t wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     if (bn) atomicAdd(&a.tot[0], (u64)__popcll(bn));
     if (bytes) atomicAdd(&a.tot[1], bytes);
     if (bp) atomicAdd(&a.tot[2], (u64)__popcll(bp));
     if (bb) atomicOr(&a.tot[3], 1ull);
-    w_cnt[wave] = (u64)__popcll(bn);
-    w_bytes[wave] = bytes;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 cnt = 0, by = 0;
-#pragma unroll
-    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
-    a.blk[2 * (u64)blockIdx.x] = cnt;
-    a.blk[2 * (u64)blockIdx.x + 1] = by;
-  }
+  block_totals_to<kStoreThreads, 2>({(u64)__popcll(bn), bytes}, a.blk);
 }
 
-// The bytes of source entry e, [*lo, *lo + size): 0 for an entry whose ends
-// are not inside the used arena (never, in a store the library filled), so
-// that no gather record points outside it.
-__device__ __forceinline__ u64 copy_extent(const PutArgs& a, uint32_t e, u64* lo) {
-  const u64 prev = e ? a.ends[e - 1] : 0, end = a.ends[e];
+// The bytes of entry e of a copy's source, [*lo, *lo + size): 0 for an entry
+// whose ends are not inside the used arena (never, in a store the library
+// filled), so that no gather record points outside it.
+__device__ __forceinline__ u64 copy_extent(const StoreView& src, uint32_t e, u64* lo) {
+  const u64 prev = e ? src.ends[e - 1] : 0, end = src.ends[e];
   *lo = prev;
-  return prev <= end && end <= a.len ? end - prev : 0;
+  return prev <= end && end <= src.bytes ? end - prev : 0;
 }
 
 // One lane per ID of a copy between stores.  tot[4] starts at UINT64_MAX.
 __global__ __launch_bounds__(kStoreThreads) void store_copy_select_kernel(PutArgs a) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
   bool is_new = false, present = false, missing = false;
   u64 size = 0;
   if (i < a.n) {
     const Id32 me = load_id(a.ids, i);
     if (a.all || idset_find(a.ids, a.n, a.slots, a.mask, a.salt, me) == (uint32_t)i) {
-      present = idset_find(a.st_ids, a.st_n, a.st_slots, a.st_mask, a.st_salt, me) != kEmpty;
+      present = store_find(a.dst, me) != kEmpty;
       if (!present) {
-        const uint32_t e = a.all ? (uint32_t)i
-                                 : idset_find(a.src_ids, a.src_n, a.src_slots, a.src_mask, a.src_salt, me);
+        const uint32_t e = a.all ? (uint32_t)i : store_find(a.src, me);
         missing = e == kEmpty;
         if (!missing) {
           u64 lo;
           is_new = true;
-          size = copy_extent(a, e, &lo);
+          size = copy_extent(a.src, e, &lo);
           a.srce[i] = e;
         }
       }
@@ -194,7 +163,6 @@ __global__ __launch_bounds__(kStoreThreads) void store_copy_select_kernel(PutArg
   }
   const u64 bn = __ballot(is_new), bp = __ballot(present), bm = __ballot(missing);
   const u64 bytes = wave_sum(size);
-  const uint32_t wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     if (bn) atomicAdd(&a.tot[0], (u64)__popcll(bn));
     if (bytes) atomicAdd(&a.tot[1], bytes);
@@ -203,44 +171,23 @@ __global__ __launch_bounds__(kStoreThreads) void store_copy_select_kernel(PutArg
       atomicAdd(&a.tot[3], (u64)__popcll(bm));
       atomicMin(&a.tot[4], i + (u64)__ffsll((unsigned long long)bm) - 1);  // (lane 0's i: the wave's first)
     }
-    w_cnt[wave] = (u64)__popcll(bn);
-    w_bytes[wave] = bytes;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 cnt = 0, by = 0;
-#pragma unroll
-    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
-    a.blk[2 * (u64)blockIdx.x] = cnt;
-    a.blk[2 * (u64)blockIdx.x + 1] = by;
-  }
+  block_totals_to<kStoreThreads, 2>({(u64)__popcll(bn), bytes}, a.blk);
 }
 
-// One workgroup: the workgroups' {chunks, bytes} pairs become their exclusive
-// prefix sums, kStoreThreads pairs a pass with a carry between passes.
-__global__ __launch_bounds__(kStoreThreads) void store_scan_kernel(u64* blk, u64 nblk) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  u64 carry_c = 0, carry_b = 0;
-  for (u64 base = 0; base < nblk; base += kStoreThreads) {
-    const u64 j = base + threadIdx.x;
-    const u64 c = j < nblk ? blk[2 * j] : 0, b = j < nblk ? blk[2 * j + 1] : 0;
-    const u64 ic = wave_scan(c), ib = wave_scan(b);
-    if (lane == 63) w_cnt[wave] = ic, w_bytes[wave] = ib;
-    __syncthreads();
-    u64 off_c = 0, off_b = 0, all_c = 0, all_b = 0;
-#pragma unroll
-    for (int w = 0; w < kStoreWaves; ++w) {
-      if ((uint32_t)w < wave) off_c += w_cnt[w], off_b += w_bytes[w];
-      all_c += w_cnt[w], all_b += w_bytes[w];
-    }
-    if (j < nblk) {
-      blk[2 * j] = carry_c + off_c + ic - c;
-      blk[2 * j + 1] = carry_b + off_b + ib - b;
-    }
-    carry_c += all_c, carry_b += all_b;
-    __syncthreads();  // (the next pass writes the wave totals again)
-  }
+// Entry e of ids[] / ends[]: its ID, its end and its gather record (size bytes
+// from src to arena offset off).
+__device__ __forceinline__ void write_entry(uint8_t* ids, uint64_t* ends, u64 e, const Id32& me, u64 off,
+                                            u64 size, const uint8_t* src, AsmSeg* seg) {
+  uint4* dst = reinterpret_cast<uint4*>(ids + 32 * e);
+  dst[0] = me.lo;
+  dst[1] = me.hi;
+  ends[e] = off + size;
+  AsmSeg g;
+  g.dst_off = off;
+  g.bytes = size;
+  g.src = src;
+  *seg = g;
 }
 
 // One lane per chunk, the grid of store_select_kernel.  Runs only after the
@@ -249,68 +196,45 @@ __global__ __launch_bounds__(kStoreThreads) void store_scan_kernel(u64* blk, u64
 // srce[i] of the source store (PutArgs), not chunk i of the blob.
 template <bool COPY>
 __global__ __launch_bounds__(kStoreThreads) void store_append_kernel(PutArgs a) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   bool is_new = false;
   u64 size = 0, prev = 0;
   if (i < a.n && a.flag[i]) {
     is_new = true;
     if constexpr (COPY) {
-      size = copy_extent(a, a.srce[i], &prev);  // (as select sized it: never reads past the used arena)
+      size = copy_extent(a.src, a.srce[i], &prev);  // (as select sized it: never reads past the used arena)
     } else {
       const u64 e = a.ends[i];
       prev = i ? a.ends[i - 1] : a.start;
       if (prev <= e && e <= a.len) size = e - prev;  // (select checked it: never reads past the blob)
     }
   }
-  const u64 bn = __ballot(is_new);
-  const u64 ib = wave_scan(size);
-  if (lane == 63) w_cnt[wave] = (u64)__popcll(bn), w_bytes[wave] = ib;
-  __syncthreads();
+  u64 before[2], all[2];
+  block_scan<kStoreThreads, 2>({is_new ? 1ull : 0ull, size}, before, all);
   if (!is_new) return;
-  u64 rank = a.blk[2 * (u64)blockIdx.x] + (u64)__popcll(bn & ((1ull << lane) - 1));
-  u64 off = a.blk[2 * (u64)blockIdx.x + 1] + ib - size;
-#pragma unroll
-  for (int w = 0; w < kStoreWaves; ++w)
-    if ((uint32_t)w < wave) rank += w_cnt[w], off += w_bytes[w];
+  const u64 rank = a.blk[2 * (u64)blockIdx.x] + before[0];
   if (rank >= a.n_new) return;  // (never: the ranks are the scan of the flags the total counted)
-  const u64 e = a.st_n + rank;
-  off += a.st_bytes;
+  const u64 e = a.dst.n + rank;
+  const u64 off = a.dst.bytes + a.blk[2 * (u64)blockIdx.x + 1] + before[1];
   const Id32 me = load_id(a.ids, i);
-  uint4* dst = reinterpret_cast<uint4*>(a.st_ids + 32 * e);
-  dst[0] = me.lo;
-  dst[1] = me.hi;
-  a.st_ends[e] = off + size;
-  AsmSeg g;
-  g.dst_off = off;
-  g.bytes = size;
-  g.src = a.blob + prev;
-  a.segs[rank] = g;
-  // the first empty slot on the probe sequence; no ID is compared (see above)
-  u64 s = hash_id(me, a.st_salt) & a.st_mask;
-  for (u64 step = 0; step <= a.st_mask; ++step, s = (s + 1) & a.st_mask) {
-    uint32_t cur = __hip_atomic_load(&a.st_slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur != kEmpty) continue;
-    cur = atomicCAS(&a.st_slots[s], kEmpty, (uint32_t)e);
-    if (cur == kEmpty) break;
-  }
+  write_entry(a.dst.ids, a.dst.ends, e, me, off, size, (COPY ? a.src.arena : a.blob) + prev, &a.segs[rank]);
+  idset_claim_empty(a.dst.slots, a.dst.mask, a.dst.salt, me, (uint32_t)e);
 }
 
 // One lane per question: ids[idx ? idx[i] : i] looked up in the store.
-__global__ __launch_bounds__(kStoreThreads) void store_lookup_kernel(
-    const uint8_t* ids, const uint32_t* idx, u64 n, const uint8_t* st_ids, const uint64_t* st_ends,
-    const uint32_t* st_slots, u64 st_n, u64 st_mask, u64 st_salt, uint64_t* offs, uint64_t* sizes,
-    u64* missing) {
+__global__ __launch_bounds__(kStoreThreads) void store_lookup_kernel(const uint8_t* ids,
+                                                                     const uint32_t* idx, u64 n,
+                                                                     StoreView st, uint64_t* offs,
+                                                                     uint64_t* sizes, u64* missing) {
   const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
   bool miss = false;
   if (i < n) {
     const Id32 key = load_id(ids, idx ? idx[i] : i);
-    const uint32_t e = idset_find(st_ids, st_n, st_slots, st_mask, st_salt, key);
+    const uint32_t e = store_find(st, key);
     miss = e == kEmpty;
-    const u64 lo = miss ? UINT64_MAX : (e ? st_ends[e - 1] : 0);
+    const u64 lo = miss ? UINT64_MAX : (e ? st.ends[e - 1] : 0);
     if (offs) offs[i] = lo;
-    if (sizes) sizes[i] = miss ? 0 : st_ends[e] - lo;
+    if (sizes) sizes[i] = miss ? 0 : st.ends[e] - lo;
   }
   const u64 bm = __ballot(miss);
   if ((threadIdx.x & 63) == 0 && bm) atomicAdd(missing, (u64)__popcll(bm));
@@ -335,10 +259,7 @@ struct PruneArgs {
   const uint32_t* slots;  // ... and the table over them
   u64 n, mask, salt;
   u64 invert;             // DSX_PRUNE_REMOVE: ids[] names the entries to drop
-  const uint8_t* st_ids;  // the store before the prune
-  const uint64_t* st_ends;
-  u64 st_n;
-  const uint8_t* arena;
+  StoreView st;           // the store before the prune (only read: the rebuild is the host's copies)
   uint8_t* flag;       // keep[e]
   u64* blk;            // {kept entries, kept bytes} per workgroup
   u64* tot;            // [kStoreCounters]
@@ -352,38 +273,26 @@ struct PruneArgs {
 // with invert).  tot[2] takes UINT64_MAX - the lowest offset of a removed entry
 // that has bytes: in front of that offset no byte moves.
 __global__ __launch_bounds__(kStoreThreads) void store_mark_kernel(PruneArgs a) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
   bool keep = false;
   u64 size = 0, gone_at = 0;
-  if (e < a.st_n) {
-    const bool named = idset_find(a.ids, a.n, a.slots, a.mask, a.salt, load_id(a.st_ids, e)) != kEmpty;
+  if (e < a.st.n) {
+    const bool named = idset_find(a.ids, a.n, a.slots, a.mask, a.salt, load_id(a.st.ids, e)) != kEmpty;
     keep = named != (a.invert != 0);
-    const u64 lo = e ? a.st_ends[e - 1] : 0, hi = a.st_ends[e];
+    const u64 lo = e ? a.st.ends[e - 1] : 0, hi = a.st.ends[e];
     if (keep) size = hi - lo;
     else if (hi > lo) gone_at = UINT64_MAX - lo;
     a.flag[e] = keep ? 1 : 0;
   }
   const u64 bk = __ballot(keep);
   const u64 bytes = wave_sum(size);
-#pragma unroll
-  for (int o = 32; o; o >>= 1) gone_at = std::max<u64>(gone_at, __shfl_down(gone_at, o, 64));
-  const uint32_t wave = threadIdx.x >> 6;
+  gone_at = wave_max(gone_at);
   if ((threadIdx.x & 63) == 0) {
     if (bk) atomicAdd(&a.tot[0], (u64)__popcll(bk));
     if (bytes) atomicAdd(&a.tot[1], bytes);
     if (gone_at) atomicMax(&a.tot[2], gone_at);
-    w_cnt[wave] = (u64)__popcll(bk);
-    w_bytes[wave] = bytes;
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u64 cnt = 0, by = 0;
-#pragma unroll
-    for (int w = 0; w < kStoreWaves; ++w) cnt += w_cnt[w], by += w_bytes[w];
-    a.blk[2 * (u64)blockIdx.x] = cnt;
-    a.blk[2 * (u64)blockIdx.x + 1] = by;
-  }
+  block_totals_to<kStoreThreads, 2>({(u64)__popcll(bk), bytes}, a.blk);
 }
 
 // One lane per entry, the grid of store_mark_kernel, after the scan: survivor e
@@ -392,60 +301,37 @@ __global__ __launch_bounds__(kStoreThreads) void store_mark_kernel(PruneArgs a) 
 // launch still has to read); every survivor leaves a gather record, those in
 // front of the first removed byte with src == the place they already have.
 __global__ __launch_bounds__(kStoreThreads) void store_compact_kernel(PruneArgs a) {
-  __shared__ u64 w_cnt[kStoreWaves], w_bytes[kStoreWaves];
   const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   bool keep = false;
   u64 size = 0, old = 0;
-  if (e < a.st_n && a.flag[e]) {
+  if (e < a.st.n && a.flag[e]) {
     keep = true;
-    old = e ? a.st_ends[e - 1] : 0;
-    size = a.st_ends[e] - old;
+    old = e ? a.st.ends[e - 1] : 0;
+    size = a.st.ends[e] - old;
   }
-  const u64 bk = __ballot(keep);
-  const u64 ib = wave_scan(size);
-  if (lane == 63) w_cnt[wave] = (u64)__popcll(bk), w_bytes[wave] = ib;
-  __syncthreads();
-  u64 rank = a.blk[2 * (u64)blockIdx.x] + (u64)__popcll(bk & ((1ull << lane) - 1));
-  u64 off = a.blk[2 * (u64)blockIdx.x + 1] + ib - size;
-#pragma unroll
-  for (int w = 0; w < kStoreWaves; ++w)
-    if ((uint32_t)w < wave) rank += w_cnt[w], off += w_bytes[w];
+  u64 before[2], all[2];
+  block_scan<kStoreThreads, 2>({keep ? 1ull : 0ull, size}, before, all);
+  const u64 rank = a.blk[2 * (u64)blockIdx.x] + before[0];
+  const u64 off = a.blk[2 * (u64)blockIdx.x + 1] + before[1];
   const bool moved = keep && off != old;
-  if (keep && rank < a.n_keep) {  // (always: the ranks are the scan of the flags the total counted)
-    const Id32 me = load_id(a.st_ids, e);
-    uint4* dst = reinterpret_cast<uint4*>(a.new_ids + 32 * rank);
-    dst[0] = me.lo;
-    dst[1] = me.hi;
-    a.new_ends[rank] = off + size;
-    AsmSeg g;
-    g.dst_off = off;
-    g.bytes = size;
-    g.src = a.arena + old;
-    a.segs[rank] = g;
-  }
+  if (keep && rank < a.n_keep)  // (always: the ranks are the scan of the flags the total counted)
+    write_entry(a.new_ids, a.new_ends, rank, load_id(a.st.ids, e), off, size, a.st.arena + old,
+                &a.segs[rank]);
   const u64 bm = __ballot(moved);
   const u64 mb = wave_sum(moved ? size : 0);
-  if (lane == 0) {
+  if ((threadIdx.x & 63) == 0) {
     if (bm) atomicAdd(&a.tot[4], (u64)__popcll(bm));
     if (mb) atomicAdd(&a.tot[5], mb);
   }
 }
 
-// One lane per entry of the compacted store: the put's claim (no ID is
-// compared: the stored IDs differ from each other) into the cleared table.
+// One lane per entry of the compacted store: the put's claim into the cleared
+// table (the stored IDs differ from each other).
 __global__ __launch_bounds__(kStoreThreads) void store_reclaim_kernel(const uint8_t* st_ids, u64 st_n,
                                                                       uint32_t* st_slots, u64 st_mask,
                                                                       u64 st_salt) {
   const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
-  if (e >= st_n) return;
-  u64 s = hash_id(load_id(st_ids, e), st_salt) & st_mask;
-  for (u64 step = 0; step <= st_mask; ++step, s = (s + 1) & st_mask) {
-    uint32_t cur = __hip_atomic_load(&st_slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur != kEmpty) continue;
-    cur = atomicCAS(&st_slots[s], kEmpty, (uint32_t)e);
-    if (cur == kEmpty) break;
-  }
+  if (e < st_n) idset_claim_empty(st_slots, st_mask, st_salt, load_id(st_ids, e), (uint32_t)e);
 }
 
 }  // namespace dsx
@@ -454,33 +340,9 @@ using namespace dsx;
 
 namespace {
 
-constexpr uint64_t kStoreMaxN = 0xFFFFFFF0ull;
 constexpr uint64_t kPruneWindow = 256ull << 20;  // dsx_store_prune's window == 0 (DESIGN.md 4.7 has the sweep)
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 inline uint32_t blocks_of(uint64_t n) { return (uint32_t)((n + kStoreThreads - 1) / kStoreThreads); }
-
-int invalid(dsx_ctx* c, const char* what) {
-  c->err = what;
-  return DSX_E_INVAL;
-}
-
-int broken(dsx_ctx* c) {
-  c->err = "the store is broken: a prune failed while it moved the arena; destroy it";
-  return DSX_E_STATE;
-}
-
-// [a, a + an) and [b, b + bn) share a byte
-bool overlaps(const void* a, uint64_t an, const void* b, uint64_t bn) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return an && bn && x < y + bn && y < x + an;
-}
-
-bool owns(const dsx_ctx* c, const dsx_store* s) {
-  const auto& live = c->store.live;
-  return std::find(live.begin(), live.end(), s) != live.end();
-}
 
 void free_store(dsx_store* s) {
   s->ids.release();
@@ -490,14 +352,34 @@ void free_store(dsx_store* s) {
   delete s;
 }
 
-// the IDs where a kernel can read them: in place, or staged in the context
-int stage_ids(dsx_ctx* c, const void* ids, uint64_t n, bool device, const uint8_t** out) {
-  *out = (const uint8_t*)ids;
-  if (device && aligned(ids, 16)) return DSX_OK;
-  IdsetScratch& t = c->idset;
-  HIPCHK(c, grow(c, t.ids, n * 32));
-  HIPCHK(c, hipMemcpyAsync(t.ids.p, ids, n * 32, hipMemcpyDefault, c->stream));
-  *out = t.ids.p;
+// The front half of a put, a copy and a prune, up to the one host wait of the
+// call before anything of a store is written: the flags, the workgroups' pairs
+// and the counters grown, the counters cleared, the caller's select (which sets
+// its arguments' flag, blk and tot from the scratch, presets a counter that
+// does not start at 0, and launches its kernel over `blocks` workgroups), the
+// array scan, the counters read back into tot[], and the wait.  distinct (a
+// prune's): the distinct IDs the call's table counted, read in the same wait.
+template <class Select>
+int select_scan_wait(dsx_ctx* c, uint64_t items, Select&& select, u64 (&tot)[kStoreCounters],
+                     u64* distinct = nullptr) {
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint32_t blocks = blocks_of(items);
+  HIPCHK(c, grow(c, w.flag, items));
+  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  if (blocks) {
+    const int rc = select(blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL(block_array_scan_kernel<2>, dim3(1), dim3(kArrayScanThreads), 0, st, w.blk.p,
+                       (u64)blocks, (u64*)nullptr);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+  if (distinct)
+    HIPCHK(c, hipMemcpyAsync(distinct, c->idset.tot.p, sizeof *distinct, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
   return DSX_OK;
 }
 
@@ -527,7 +409,7 @@ void store_release(dsx_ctx* c) {
 extern "C" int dsx_store_create(dsx_ctx_t* c, uint64_t arena_bytes, uint64_t max_chunks,
                                 dsx_store_t** out) {
   DSX_FLUSH_BEHIND(c);
-  if (!c || !out || max_chunks > kStoreMaxN) return DSX_E_INVAL;
+  if (!c || !out || max_chunks > kCallMaxN) return DSX_E_INVAL;
   *out = nullptr;
   HIPCHK(c, hipSetDevice(c->device));
   c->err.clear();
@@ -561,7 +443,7 @@ extern "C" int dsx_store_destroy(dsx_ctx_t* c, dsx_store_t* s) {
   if (!c || !s) return DSX_E_INVAL;
   auto& live = c->store.live;
   auto it = std::find(live.begin(), live.end(), s);
-  if (it == live.end()) return invalid(c, "the store belongs to another context");
+  if (it == live.end()) return foreign_store(c, DSX_E_INVAL);
   live.erase(it);
   HIPCHK(c, hipSetDevice(c->device));
   (void)hipStreamSynchronize(c->stream);
@@ -595,9 +477,9 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
   if (!c || !s) return DSX_E_INVAL;
   if (totals) *totals = dsx_store_put_totals_t{};
   if ((flags & ~(f_ids | f_ends)) != 0) return invalid(c, "unknown flag bit");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
-  if (n > kStoreMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (n > kCallMaxN) return invalid(c, "more chunks than a call takes (0xFFFFFFF0)");
   if (n && (!ids || !ends)) return invalid(c, "the IDs or the chunk ends are missing");
   if (len && !d_blob) return invalid(c, "the blob is missing");
   if (len > UINT64_MAX - (uintptr_t)d_blob) return invalid(c, "the blob wraps the address space");
@@ -618,57 +500,36 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
   StoreScratch& w = c->store;
   hipStream_t st = c->stream;
 
-  const uint8_t* d_ids = nullptr;
-  int rc = stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  PutArgs a{};
+  int rc = stage_ids(c, ids, n, (flags & f_ids) != 0, &a.ids);
   if (rc) return rc;
-  const uint64_t* d_ends = ends;
-  if (!(flags & f_ends) || !aligned(ends, 8)) {
-    HIPCHK(c, grow(c, t.ends, n));
-    HIPCHK(c, hipMemcpyAsync(t.ends.p, ends, n * 8, hipMemcpyDefault, st));
-    d_ends = t.ends.p;
-  }
+  rc = stage_ends(c, ends, n, (flags & f_ends) != 0, &a.ends);
+  if (rc) return rc;
   const uint32_t blocks = blocks_of(n);
   const uint64_t cap = idset_table_cap(n);
   HIPCHK(c, grow(c, t.slots, cap));
   HIPCHK(c, grow(c, t.tot, kIdsetCounters));
-  HIPCHK(c, grow(c, w.flag, n));
-  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
-  HIPCHK(c, grow(c, w.tot, kStoreCounters));
 
-  // ---- select ------------------------------------------------------------------
-  const uint64_t salt = idset_next_salt();
-  rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  // ---- select, scan ------------------------------------------------------------
+  a.salt = idset_next_salt();
+  rc = idset_enqueue_build(c, a.ids, n, t.slots.p, cap, a.salt, t.tot.p);
   if (rc) return rc;
-  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
-  PutArgs a{};
-  a.ids = d_ids;
-  a.ends = d_ends;
   a.start = start;
   a.n = n;
   a.len = len;
   a.blob = (const uint8_t*)d_blob;
   a.slots = t.slots.p;
   a.mask = cap - 1;
-  a.salt = salt;
-  a.st_ids = s->ids.p;
-  a.st_ends = s->ends.p;
-  a.st_slots = s->slots.p;
-  a.st_n = s->chunks;
-  a.st_mask = s->cap - 1;
-  a.st_salt = s->salt;
-  a.st_bytes = s->bytes;
-  a.flag = w.flag.p;
-  a.blk = w.blk.p;
-  a.tot = w.tot.p;
-  hipLaunchKernelGGL(store_select_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
-  HIPCHK(c, hipGetLastError());
-  // ---- scan --------------------------------------------------------------------
-  hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
-  HIPCHK(c, hipGetLastError());
+  a.dst = view_of(s);
   // ---- the one wait before any byte is copied ----------------------------------
   u64 tot[kStoreCounters] = {};
-  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  rc = select_scan_wait(c, n, [&](uint32_t grid) -> int {
+    a.flag = w.flag.p, a.blk = w.blk.p, a.tot = w.tot.p;
+    hipLaunchKernelGGL(store_select_kernel, dim3(grid), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+    return DSX_OK;
+  }, tot);
+  if (rc) return rc;
   if (tot[3]) return invalid(c, "chunk ends must be non-decreasing, start <= ends[0], ends[n-1] <= len");
   const uint64_t stored = tot[0], stored_bytes = tot[1], present = tot[2];
   if (totals) {
@@ -707,9 +568,7 @@ static int enqueue_lookup(dsx_ctx* c, const dsx_store* s, const uint8_t* d_ids, 
   HIPCHK(c, grow(c, w.tot, kStoreCounters));
   HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), c->stream));
   hipLaunchKernelGGL(store_lookup_kernel, dim3(blocks_of(m)), dim3(kStoreThreads), 0, c->stream, d_ids,
-                     d_idx, (u64)m, (const uint8_t*)s->ids.p, (const uint64_t*)s->ends.p,
-                     (const uint32_t*)s->slots.p, (u64)s->chunks, (u64)(s->cap - 1), (u64)s->salt,
-                     d_offs, d_sizes, w.tot.p);
+                     d_idx, (u64)m, view_of(s), d_offs, d_sizes, w.tot.p);
   HIPCHK(c, hipGetLastError());
   return DSX_OK;
 }
@@ -722,9 +581,9 @@ extern "C" int dsx_store_locate(dsx_ctx_t* c, const dsx_store_t* s, const void* 
   if (!c || !s) return DSX_E_INVAL;
   if (n_missing) *n_missing = 0;
   if ((flags & ~(f_ids | f_out)) != 0) return invalid(c, "unknown flag bit");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
-  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (n > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if (n && !ids) return invalid(c, "the IDs are missing");
   if (n == 0) return DSX_OK;
   HIPCHK(c, hipSetDevice(c->device));
@@ -761,8 +620,8 @@ extern "C" int dsx_store_entries(dsx_ctx_t* c, const dsx_store_t* s, uint64_t fi
   DSX_FLUSH_BEHIND(c);
   if (!c || !s) return DSX_E_INVAL;
   if ((flags & ~DSX_OUT_DEVICE) != 0) return invalid(c, "unknown flag bit");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
   if (first > s->chunks || n > s->chunks - first)
     return invalid(c, "first + n is beyond the store's entries");
   if (n == 0) return DSX_OK;
@@ -784,9 +643,9 @@ extern "C" int dsx_store_resolve(dsx_ctx_t* c, const dsx_store_t* s, const void*
   if (n_wrong_size) *n_wrong_size = 0;
   if (first_bad) *first_bad = 0xFFFFFFFFu;
   if ((flags & ~DSX_IDS_DEVICE) != 0) return invalid(c, "unknown flag bit");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
-  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (n > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if ((n && !ids) || (nsegs && !segs)) return invalid(c, "the IDs or the segments are missing");
   try {
     std::vector<uint32_t> idx;    // the store segments' target positions ...
@@ -851,8 +710,8 @@ extern "C" int dsx_store_verify(dsx_ctx_t* c, const dsx_store_t* s, int algo, ui
   if (n_bad) *n_bad = 0;
   if (algo != DSX_DIGEST_SHA512_256 && algo != DSX_DIGEST_SHA256)
     return invalid(c, "algo names no digest");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
   if (cap && !bad) return invalid(c, "the list of bad entries is missing");
   const uint64_t n = s->chunks;
   if (n == 0) return DSX_OK;
@@ -893,18 +752,6 @@ extern "C" int dsx_store_verify(dsx_ctx_t* c, const dsx_store_t* s, int algo, ui
   }
 }
 
-// grow() without the headroom: prune's scratch is sized by its arguments
-template <class T>
-static hipError_t fit(dsx_ctx* c, DevBuf<T>& b, size_t n) {
-  if (b.p && b.n >= n) return hipSuccess;
-  if (b.p) {
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipStreamSynchronize(c->copy_stream);
-    if (c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
-  }
-  return b.ensure(n);
-}
-
 extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, uint64_t n,
                                uint64_t window, dsx_store_prune_totals_t* totals, uint32_t flags) {
   const uint32_t f_ids = DSX_IDS_DEVICE, f_rm = DSX_PRUNE_REMOVE;
@@ -912,9 +759,9 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
   DSX_FLUSH_BEHIND(c);
   if (totals) *totals = dsx_store_prune_totals_t{};
   if ((flags & ~(f_ids | f_rm)) != 0) return invalid(c, "unknown flag bit");
-  if (!owns(c, s)) return invalid(c, "the store belongs to another context");
-  if (s->broken) return broken(c);
-  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (n > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if (n && !ids) return invalid(c, "the IDs are missing");
   HIPCHK(c, hipSetDevice(c->device));
   c->err.clear();
@@ -924,45 +771,30 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
   const uint64_t entries = s->chunks, T = DSX_ASSEMBLE_TILE;
 
   // ---- mark, scan --------------------------------------------------------------
-  const uint8_t* d_ids = nullptr;
-  int rc = n ? stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids) : DSX_OK;
+  PruneArgs a{};
+  int rc = n ? stage_ids(c, ids, n, (flags & f_ids) != 0, &a.ids) : DSX_OK;
   if (rc) return rc;
   const uint32_t blocks = blocks_of(entries);
   const uint64_t cap = idset_table_cap(n);
   HIPCHK(c, grow(c, t.slots, cap));
   HIPCHK(c, grow(c, t.tot, kIdsetCounters));
-  HIPCHK(c, grow(c, w.flag, entries));
-  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
-  HIPCHK(c, grow(c, w.tot, kStoreCounters));
-  const uint64_t salt = idset_next_salt();
-  rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, salt, t.tot.p);
+  a.salt = idset_next_salt();
+  rc = idset_enqueue_build(c, a.ids, n, t.slots.p, cap, a.salt, t.tot.p);
   if (rc) return rc;
-  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
-  PruneArgs a{};
-  a.ids = d_ids;
   a.slots = t.slots.p;
   a.n = n;
   a.mask = cap - 1;
-  a.salt = salt;
   a.invert = (flags & f_rm) ? 1 : 0;
-  a.st_ids = s->ids.p;
-  a.st_ends = s->ends.p;
-  a.st_n = entries;
-  a.arena = s->arena.p;
-  a.flag = w.flag.p;
-  a.blk = w.blk.p;
-  a.tot = w.tot.p;
-  if (blocks) {
-    hipLaunchKernelGGL(store_mark_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
-    HIPCHK(c, hipGetLastError());
-  }
+  a.st = view_of(s);
   // ---- the one wait before anything moves ---------------------------------------
   u64 tot[kStoreCounters] = {}, distinct = 0;
-  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(&distinct, t.tot.p, sizeof distinct, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  rc = select_scan_wait(c, entries, [&](uint32_t grid) -> int {
+    a.flag = w.flag.p, a.blk = w.blk.p, a.tot = w.tot.p;
+    hipLaunchKernelGGL(store_mark_kernel, dim3(grid), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+    return DSX_OK;
+  }, tot, &distinct);
+  if (rc) return rc;
   const uint64_t kept = tot[0], kept_bytes = tot[1];
   if (kept > entries || kept_bytes > s->bytes) return invalid(c, "the store's entries are inconsistent");
   const uint64_t removed = entries - kept;
@@ -984,10 +816,11 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
   const uint64_t first_off = tot[2] ? UINT64_MAX - tot[2] : kept_bytes;  // in front of it nothing moves
   const bool moves = first_off < kept_bytes;
   if (kept) {
-    HIPCHK(c, fit(c, w.pids, kept * 32));
-    HIPCHK(c, fit(c, w.pends, kept));
+    // (no headroom: these are sized by the store and the window, not by a call that may grow)
+    HIPCHK(c, grow(c, w.pids, kept * 32, false));
+    HIPCHK(c, grow(c, w.pends, kept, false));
     HIPCHK(c, grow(c, w.segs, 3 * kept));
-    if (moves) HIPCHK(c, fit(c, w.bounce, win));
+    if (moves) HIPCHK(c, grow(c, w.bounce, win, false));
     a.new_ids = w.pids.p;
     a.new_ends = (uint64_t*)w.pends.p;
     a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
@@ -1054,11 +887,11 @@ extern "C" int dsx_store_copy(dsx_ctx_t* c, dsx_store_t* dst, const dsx_store_t*
   totals->first_missing = UINT64_MAX;
   if ((flags & ~(f_ids | f_all)) != 0) return invalid(c, "unknown flag bit");
   if (dst == src) return invalid(c, "the source and the destination are the same store");
-  if (!owns(c, dst) || !owns(c, src)) return invalid(c, "the store belongs to another context");
-  if (dst->broken || src->broken) return broken(c);
+  if (!owns(c, dst) || !owns(c, src)) return foreign_store(c, DSX_E_INVAL);
+  if (dst->broken || src->broken) return broken_store(c);
   const bool all = (flags & f_all) != 0;
   if (all && (ids || n)) return invalid(c, "copying all entries takes no IDs: ids == NULL and n == 0");
-  if (n > kStoreMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
   if (n && !ids) return invalid(c, "the IDs are missing");
   if (all) n = src->chunks;
   totals->total = n;
@@ -1069,59 +902,39 @@ extern "C" int dsx_store_copy(dsx_ctx_t* c, dsx_store_t* dst, const dsx_store_t*
   StoreScratch& w = c->store;
   hipStream_t st = c->stream;
 
-  const uint8_t* d_ids = src->ids.p;
-  int rc = all ? DSX_OK : stage_ids(c, ids, n, (flags & f_ids) != 0, &d_ids);
+  PutArgs a{};
+  a.ids = src->ids.p;
+  int rc = all ? DSX_OK : stage_ids(c, ids, n, (flags & f_ids) != 0, &a.ids);
   if (rc) return rc;
   const uint32_t blocks = blocks_of(n);
   const uint64_t cap = idset_table_cap(n);
-  HIPCHK(c, grow(c, w.flag, n));
   HIPCHK(c, grow(c, w.srce, n));
-  HIPCHK(c, grow(c, w.blk, 2 * (uint64_t)blocks));
-  HIPCHK(c, grow(c, w.tot, kStoreCounters));
 
   // ---- select, scan ------------------------------------------------------------
-  PutArgs a{};
-  a.ids = d_ids;
   a.n = n;
   a.all = all ? 1 : 0;
   if (!all) {
     HIPCHK(c, grow(c, t.slots, cap));
     HIPCHK(c, grow(c, t.tot, kIdsetCounters));
     a.salt = idset_next_salt();
-    rc = idset_enqueue_build(c, d_ids, n, t.slots.p, cap, a.salt, t.tot.p);
+    rc = idset_enqueue_build(c, a.ids, n, t.slots.p, cap, a.salt, t.tot.p);
     if (rc) return rc;
     a.slots = t.slots.p;
     a.mask = cap - 1;
-    a.src_slots = src->slots.p;
   }
-  a.ends = src->ends.p;
-  a.len = src->bytes;
-  a.blob = src->arena.p;
-  a.src_ids = src->ids.p;
-  a.src_n = src->chunks;
-  a.src_mask = src->cap - 1;
-  a.src_salt = src->salt;
-  a.st_ids = dst->ids.p;
-  a.st_ends = dst->ends.p;
-  a.st_slots = dst->slots.p;
-  a.st_n = dst->chunks;
-  a.st_mask = dst->cap - 1;
-  a.st_salt = dst->salt;
-  a.st_bytes = dst->bytes;
-  a.flag = w.flag.p;
+  a.src = view_of(src);
+  a.dst = view_of(dst);
   a.srce = w.srce.p;
-  a.blk = w.blk.p;
-  a.tot = w.tot.p;
-  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
-  HIPCHK(c, hipMemsetAsync(w.tot.p + 4, 0xFF, sizeof(u64), st));  // first_missing: none
-  hipLaunchKernelGGL(store_copy_select_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(store_scan_kernel, dim3(1), dim3(kStoreThreads), 0, st, w.blk.p, (u64)blocks);
-  HIPCHK(c, hipGetLastError());
   // ---- the one wait before dst is written anywhere -------------------------------
   u64 tot[kStoreCounters] = {};
-  HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
+  rc = select_scan_wait(c, n, [&](uint32_t grid) -> int {
+    a.flag = w.flag.p, a.blk = w.blk.p, a.tot = w.tot.p;
+    HIPCHK(c, hipMemsetAsync(w.tot.p + 4, 0xFF, sizeof(u64), st));  // first_missing: none
+    hipLaunchKernelGGL(store_copy_select_kernel, dim3(grid), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+    return DSX_OK;
+  }, tot);
+  if (rc) return rc;
   const uint64_t copied = tot[0], copied_bytes = tot[1];
   totals->copied = copied;
   totals->copied_bytes = copied_bytes;

@@ -187,12 +187,21 @@ def test_whole_blob(world, store, dctx):
     assert _torch().equal(got, whole) and np.array_equal(got.cpu().numpy(), world.blob)
 
 
-def test_many_small(world, store):
+@pytest.mark.parametrize("nranges", [1, 63, 64, 65, 255, 256, 257, 513, 4096, 65537])
+def test_many_small(world, store, nranges):
+    """Packed ranges at random offsets.  The counts are the store tests' scan
+    edges: a wave, a workgroup of the count (256 ranges), and at 65,537 ranges
+    257 workgroups, so the array scan over their sums takes a second pass with a
+    carry.  Lengths of 0 to 300 bytes: a range of length 0 takes no table slot."""
     rng = np.random.default_rng(5)
-    lens = rng.integers(1, 513, 4096)
+    lens = rng.integers(1, 513, 4096) if nranges == 4096 else rng.integers(0, 301, nranges)
     offs = [int(rng.integers(0, BLOB - ln + 1)) for ln in lens]
     tot = check_read(world, store, list(zip(offs, lens.tolist())))
-    assert tot["ranges"] == 4096 and tot["pieces"] > 4096
+    assert tot["ranges"] == nranges
+    if nranges == 4096:
+        assert tot["pieces"] > 4096
+    if nranges == 65537:  # (not one slot a range throughout: some ranges cross a chunk end)
+        assert tot["pieces"] > 65537 - int((lens == 0).sum())
 
 
 def test_null_chunks(world, store):
