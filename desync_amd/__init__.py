@@ -17,6 +17,7 @@ mirror of the reference's Go API for that path:
     NewIndexSeed, NewSeedSequencer, Plan, AssembleBlob      (fileseed.go, sequencer.go, assemble.go)
     DeviceStore, ChopBlob, ChunkMissing (a chunk store in HBM)  (store.go, local.go, chop.go, errors.go)
     IndexFromBlobs, ChopBlobs, cut_device_many (many blobs per call)  (make.go, chop.go)
+    chunk_ids_known, DeviceStore.chunk_ids (IDs by comparison with the store)  (make.go:223, chunkstorage.go:44-67)
     DeviceStore.Prune, RemoveChunk, Verify(repair=True)     (local.go, cmd/desync/prune.go)
     NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
     DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
@@ -37,7 +38,7 @@ from .hash import Hash, NewHash  # noqa: F401
 from .info import IDSet, Info, dedup  # noqa: F401
 from .extract import AssembleBlob, IndexSeed, NewIndexSeed, NewSeedSequencer, Plan, SeedInvalid, SeedSequencer, \
     Segment, StorageError  # noqa: F401
-from .store import ChopBlob, ChopBlobs, DeviceStore  # noqa: F401
+from .store import ChopBlob, ChopBlobs, DeviceStore, chunk_ids_known  # noqa: F401
 from .copy import Cache, Copy, NewCache  # noqa: F401
 from .readseeker import Cat, DeviceIndex, IndexPos, NewIndexReadSeeker, read_ranges  # noqa: F401
 from .encrypt import AEADConverter, AuthenticationError, Compressor, Converters, EncryptionKeySize, NewAES256GCM, \
@@ -53,6 +54,6 @@ __all__ = [
     "NewIndexSeed", "IndexSeed", "NewSeedSequencer", "SeedSequencer", "Plan", "Segment", "SeedInvalid",
     "AssembleBlob", "DeviceStore", "ChopBlob", "ChunkMissing", "Copy", "Cache", "NewCache",
     "EncryptionKeySize", "NewXChaCha20Poly1305", "NewAES256GCM", "AEADConverter", "Compressor", "Converters",
-    "StoreOptions", "AuthenticationError", "IndexFromBlobs", "ChopBlobs", "cut_device_many",
+    "StoreOptions", "AuthenticationError", "IndexFromBlobs", "ChopBlobs", "cut_device_many", "chunk_ids_known",
     "StorageError", "NewIndexReadSeeker", "IndexPos", "Cat", "read_ranges", "DeviceIndex",
 ]

@@ -64,6 +64,7 @@ EXPORTS = (
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
     "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305", "dsx_cut_device_many",
     "dsx_inplace_plan", "dsx_assemble_inplace", "dsx_chunk_keep", "dsx_read_ranges", "dsx_read_plan",
+    "dsx_chunk_ids_known",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -89,6 +90,10 @@ DSX_AEAD_XCHACHA20_POLY1305 = 0
 DSX_AEAD_NONCE = 24
 DSX_AEAD_OVERHEAD = 40     # nonce + tag
 DSX_AEAD_TILE = 262144     # plaintext bytes one workgroup of the seal / open main pass owns
+DSX_KNOWN_TILE = 65536     # pair bytes one workgroup of dsx_chunk_ids_known's compare owns
+DSX_KNOWN_TRIES = 4        # entries compared with one chunk at most
+DSX_KNOWN_PROBES = 64      # table slots an insert or a probe visits at most
+DSX_OFF_NONE = 0xFFFFFFFFFFFFFFFF  # known_off / dsx_store_locate: the store lacks the ID
 
 
 class Params(ctypes.Structure):
@@ -204,6 +209,14 @@ class ReadPiece(ctypes.Structure):
 
     _fields_ = [("chunk_off", ctypes.c_uint64), ("dst_off", ctypes.c_uint64),
                 ("bytes", ctypes.c_uint64), ("range", ctypes.c_uint32), ("chunk", ctypes.c_uint32)]
+
+
+class KnownTotals(ctypes.Structure):
+    """dsx_known_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("chunks", "recognised", "recognised_bytes", "hashed", "hashed_bytes", "pairs",
+                 "compared_bytes", "fp_false", "untried", "reserved")]
 
 
 class ManyOpts(ctypes.Structure):
@@ -402,6 +415,8 @@ def lib():
             "dsx_read_ranges": (i32, [vp, vp, vp, vp, u64, u64, vp, u64, vp, u64, vp, u64,
                                       P(ReadTotals), u32]),
             "dsx_read_plan": (i32, [vp, u64, u64, vp, u64, vp, u64, P(u64)]),
+            "dsx_chunk_ids_known": (i32, [vp, vp, vp, u64, u64, vp, u64, i32, vp, vp,
+                                          P(KnownTotals), u32]),
             "dsx_aead_seal": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, u32]),
             "dsx_aead_open": (i32, [vp, i32, vp, vp, u64, vp, u64, u64, vp, u64, vp, vp, u64,
                                     P(u64), u32]),

@@ -269,6 +269,7 @@ extern "C" int dsx_ctx_destroy(dsx_ctx_t* c) {
   stream_release(c);
   store_release(c);
   aead_release(c);
+  known_release(c);
   many_release(c);
   idset_release(c);
   if (c->h_state) (void)hipHostFree(c->h_state);
@@ -361,7 +362,8 @@ static uint64_t ctx_device_bytes(const dsx_ctx* c) {
   for (const auto& k : c->sh.kept) add(k.cnt), add(k.list);
   add(c->d_seam), add(c->d_all), add(c->zero_word), add(c->d_ext), add(c->d_info), add(c->d_emit);
   add(c->stamp_ring), add(c->idx_win[0]), add(c->idx_win[1]), add(c->idx_snap);
-  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c) + many_device_bytes(c);
+  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c) + many_device_bytes(c) +
+         known_device_bytes(c);
 }
 
 extern "C" int dsx_get_stats(dsx_ctx_t* c, dsx_stats_t* out) {
@@ -717,7 +719,10 @@ extern "C" int dsx_gen_dedup(dsx_ctx_t* c, void* d_dst, uint64_t offset, uint64_
 // (the grid is sized from it; with da.range_lo the count is read on the
 // device).
 int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream_t stream,
-                  uint32_t* queue, bool serial, uint32_t max_blocks, int pc) {
+                  uint32_t* queue, bool serial, uint32_t max_blocks, int pc, uint64_t work) {
+  // the chunks that are hashed size the grid and choose the kernel: max_n, or
+  // with a take mask the number it takes
+  if (!work || work > max_n) work = max_n;
   // the ctx stream, or a stream whose digests the caller runs one after
   // another (serial: dsx_index_*'s digest stream): the size-order scratch
   // (dg_order, dg_cls) is then never used by two launches at once
@@ -731,8 +736,8 @@ int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream
   // per CU, up to digest_pc_chunks chunks per lane of the grid
   const uint64_t pc_lanes = (uint64_t)c->ncu * 64u;
   if (c->digest_pc >= 0) pc = c->digest_pc > 0 ? 1 : 0;  // (DSX_DIGEST_PC)
-  if (pc > 0 || (pc < 0 && max_n <= pc_lanes * (uint64_t)c->digest_pc_chunks)) {
-    uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((max_n + 63) / 64, c->ncu));
+  if (pc > 0 || (pc < 0 && work <= pc_lanes * (uint64_t)c->digest_pc_chunks)) {
+    uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((work + 63) / 64, c->ncu));
     if (max_blocks) blocks = std::min<uint64_t>(blocks, max_blocks);
     HIPCHK(c, hipMemsetAsync(queue, 0, 4, stream));
     da.queue = queue;
@@ -766,7 +771,7 @@ int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream
   HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kDigestThreads, 0));
   if (per_cu < 1) per_cu = 1;
   uint64_t blocks = std::max<uint64_t>(
-      1, std::min<uint64_t>((max_n + kDigestThreads - 1) / kDigestThreads,
+      1, std::min<uint64_t>((work + kDigestThreads - 1) / kDigestThreads,
                             (uint64_t)per_cu * (uint64_t)c->ncu));
   if (max_blocks) blocks = std::min<uint64_t>(blocks, max_blocks);
   HIPCHK(c, hipMemsetAsync(queue, 0, 4, stream));
@@ -780,6 +785,8 @@ int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream
     HIPCHK(c, grow(c, c->dg_order, max_n));
     HIPCHK(c, c->dg_cls.ensure(2 * kSizeClasses));
     HIPCHK(c, hipMemsetAsync(c->dg_cls.p, 0, kSizeClasses * sizeof(uint32_t), stream));
+    // (a take mask: the order lists the chunks taken and ends at the first 0xFFFFFFFF)
+    if (da.take) HIPCHK(c, hipMemsetAsync(c->dg_order.p, 0xFF, max_n * sizeof(uint32_t), stream));
     const dim3 tiles((uint32_t)((max_n + kOrderTile - 1) / kOrderTile));
     hipLaunchKernelGGL(digest_order_count_kernel, tiles, dim3(256), 0, stream, da, c->dg_cls.p);
     hipLaunchKernelGGL(digest_order_scan_kernel, dim3(1), dim3(kSizeClasses), 0, stream,

@@ -31,6 +31,10 @@ struct DigestArgs {
   // chunks longer than this get no ID here (0: none): the index pipeline
   // hashes them on the host (dsx_index.cpp, host tail)
   uint64_t skip_above;
+  // one byte per chunk (null: every chunk): a chunk whose byte is 0 gets no ID
+  // here and is left out of the longest-first order (dsx_known.hip hashes only
+  // the chunks it did not recognise)
+  const uint8_t* take;
 };
 
 // Longest-first order of a digest range (LPT): a counting sort of the chunks

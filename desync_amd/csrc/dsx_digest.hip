@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256) void digest_order_count_kernel(DigestArgs a, u
   const DigestRange r = digest_range(a);
   const uint64_t t0 = (uint64_t)blockIdx.x * kOrderTile;
   for (uint64_t i = t0 + threadIdx.x; i < r.n && i < t0 + kOrderTile; i += blockDim.x)
-    atomicAdd(&h[chunk_class(r, i)], 1u);
+    if (!a.take || a.take[i]) atomicAdd(&h[chunk_class(r, i)], 1u);
   __syncthreads();
   for (int c = threadIdx.x; c < kSizeClasses; c += blockDim.x)
     if (h[c]) atomicAdd(&cls_count[c], h[c]);
@@ -528,11 +528,13 @@ __global__ __launch_bounds__(256) void digest_order_scatter_kernel(DigestArgs a,
   const DigestRange r = digest_range(a);
   const uint64_t t0 = (uint64_t)blockIdx.x * kOrderTile;
   uint32_t cls[PER], rank[PER];
+  bool in[PER];  // (a.take: the order lists the chunks taken only; the host filled the rest with 0xFFFFFFFF)
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const uint64_t i = t0 + (uint64_t)q * 256u + threadIdx.x;
-    cls[q] = i < r.n ? chunk_class(r, i) : 0u;
-    rank[q] = i < r.n ? atomicAdd(&h[cls[q]], 1u) : 0u;
+    in[q] = i < r.n && (!a.take || a.take[i]);
+    cls[q] = in[q] ? chunk_class(r, i) : 0u;
+    rank[q] = in[q] ? atomicAdd(&h[cls[q]], 1u) : 0u;
   }
   __syncthreads();
   for (int c = threadIdx.x; c < kSizeClasses; c += blockDim.x)
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(256) void digest_order_scatter_kernel(DigestArgs a,
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const uint64_t i = t0 + (uint64_t)q * 256u + threadIdx.x;
-    if (i < r.n) order[base[cls[q]] + rank[q]] = (uint32_t)i;
+    if (in[q]) order[base[cls[q]] + rank[q]] = (uint32_t)i;
   }
 }
 
@@ -580,6 +582,11 @@ __global__ __launch_bounds__(kDigestThreads) void digest_kernel(DigestArgs a) {
     ci = n;
     while (k < n) {
       ci = a.order ? (uint64_t)a.order[k] : k;
+      if (a.take && (ci >= n || !a.take[ci])) {  // the order's end, or a chunk not taken
+        k = ci >= n ? n : (uint64_t)nfirst + atomicAdd(a.queue, 1u);
+        ci = n;
+        continue;
+      }
       const uint64_t sa = ci == 0 ? first_start : ends[ci - 1], ea = ends[ci];
       if (a.skip_above && sa <= ea && ea - sa > a.skip_above) {  // hashed on the host
         k = (uint64_t)nfirst + atomicAdd(a.queue, 1u);
@@ -718,6 +725,10 @@ __global__ __launch_bounds__(128, 1) void digest_pc_kernel(DigestArgs a) {
   bool have_next = false, fresh = true;
   auto start_chunk = [&]() {
     while (ci < n) {
+      if (a.take && !a.take[ci]) {  // not taken
+        ci = (uint64_t)nfirst + atomicAdd(a.queue, 1u);
+        continue;
+      }
       const uint64_t sa = ci == 0 ? first_start : ends[ci - 1], ea = ends[ci];
       if (a.skip_above && sa <= ea && ea - sa > a.skip_above) {  // hashed on the host
         ci = (uint64_t)nfirst + atomicAdd(a.queue, 1u);

@@ -98,6 +98,7 @@ using namespace dsx_host;
 #include "dsx_idset.h"
 #include "dsx_store.h"
 #include "dsx_aead.h"
+#include "dsx_known.h"
 
 // A piece's candidate lists kept past its call (shards: the O(candidates)
 // re-walk re-runs only the stitch over them)
@@ -344,6 +345,7 @@ struct dsx_ctx {
   IdsetScratch idset;  // chunk-ID sets (dsx_idset.hip)
   StoreScratch store;  // chunk stores (dsx_store.hip)
   AeadScratch aead;    // the AEAD store converter (dsx_aead.hip)
+  KnownScratch known;  // chunk IDs by comparison (dsx_known.hip)
 };
 
 // Grow a device buffer; outstanding work may still use the old allocation, so
@@ -455,8 +457,11 @@ int launch_stitch(dsx_ctx* c, const CallCfg& cc, const PieceCands& pc, uint64_t 
                   bool is_last, uint64_t seq, bool trace);
 // digest_kernel on `stream` (null: the ctx stream) with queue counter `queue`
 // (null: the ctx's); max_n bounds the chunk count (sizes the grid); pc: 1
-// digest_pc_kernel, 0 digest_kernel, -1 by max_n (DSX_DIGEST_PC overrides)
+// digest_pc_kernel, 0 digest_kernel, -1 by max_n (DSX_DIGEST_PC overrides);
+// work: with da.take the number of chunks the mask takes (0: max_n), which then
+// sizes the grid and chooses the kernel in max_n's place
 int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream_t stream = nullptr,
-                  uint32_t* queue = nullptr, bool serial = false, uint32_t max_blocks = 0, int pc = -1);
+                  uint32_t* queue = nullptr, bool serial = false, uint32_t max_blocks = 0, int pc = -1,
+                  uint64_t work = 0);
 void index_release(dsx_ctx* c);   // dsx_index.cpp: frees the pipeline's buffers
 void stream_release(dsx_ctx* c);  // dsx_stream.cpp: frees the stream's buffers

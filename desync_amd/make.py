@@ -228,14 +228,20 @@ def _blob_heads(t, starts, lens):
     return {int(b): heads[k].tobytes() for k, b in enumerate(which)}
 
 
-def _index_blobs(blobs, min_size, avg_size, max_size, ctx):
+def _index_blobs(blobs, min_size, avg_size, max_size, ctx, known=None):
     """IndexFromBlobs' work: -> (indexes, pointer, length, global ends, ids,
     tensor kept alive)."""
+    if known is not None:
+        if ctx is not None and ctx is not known.ctx:
+            raise ValueError("known= is a store of the context the call runs on")
+        ctx = known.ctx
     ctx = ctx or _lib.default_context()
     ptr, length, be, t = _pack_blobs(blobs, ctx)
     ends, first, _ = cut_device_many(ptr, length, be, min_size, avg_size, max_size, ctx=ctx)
     ids = np.empty((ends.size, 32), dtype=np.uint8)
-    if ends.size:
+    if ends.size and known is not None:
+        ids = known.chunk_ids((ptr, length), ends, 0)[0]
+    elif ends.size:
         check(lib().dsx_chunk_ids(ctx.h, ctypes.c_void_p(ptr), length, 0, ends.ctypes.data, ends.size,
                                   ids.ctypes.data, 0, _digest_code()), ctx.h)
     starts = np.concatenate([np.zeros(1, dtype=np.uint64), be[:-1]]) if be.size else be
@@ -252,7 +258,7 @@ def _index_blobs(blobs, min_size, avg_size, max_size, ctx):
     return out, ptr, length, ends, ids, t
 
 
-def IndexFromBlobs(blobs, min_size, avg_size, max_size, ctx=None):
+def IndexFromBlobs(blobs, min_size, avg_size, max_size, ctx=None, known=None):
     """IndexFromFile (make.go:22-163) for many blobs in HBM at once: one Index
     per blob, each equal to what IndexFromFile gives for that blob's bytes
     alone (chunk offsets relative to the blob; an empty blob gives the index
@@ -264,8 +270,13 @@ def IndexFromBlobs(blobs, min_size, avg_size, max_size, ctx=None):
     or one upload: that costs a copy of every byte.  Then one
     dsx_cut_device_many call cuts every blob, one dsx_chunk_ids call hashes
     every chunk, and one gather fetches each blob's first 64 bytes for the
-    catar flag sniff of make.go:49-62."""
-    return _index_blobs(blobs, min_size, avg_size, max_size, ctx)[0]
+    catar flag sniff of make.go:49-62.
+
+    ``known``: a :class:`DeviceStore` that may already hold some of the chunks
+    (the previous version's).  The IDs then come from dsx_chunk_ids_known: a
+    chunk whose bytes the store holds is compared with them instead of hashed.
+    The indexes are the same either way."""
+    return _index_blobs(blobs, min_size, avg_size, max_size, ctx, known)[0]
 
 
 def chunk_ids(ptr, length, ends, start=0, ctx=None, algo=None):

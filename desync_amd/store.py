@@ -242,6 +242,12 @@ class DeviceStore:
                                           flags), self.ctx)
         return offs, sizes, miss.value
 
+    def chunk_ids(self, blob, ends, start=0, n=None, algo=None, device_out=False):
+        """:func:`chunk_ids_known` against this store, under its lock
+        -> (ids, known_off, totals)."""
+        with self._lock:
+            return chunk_ids_known(self, blob, ends, start, n, algo, device_out)
+
     def HasChunk(self, cid) -> bool:
         cid = bytes(cid)
         miss = ctypes.c_uint64()
@@ -586,7 +592,65 @@ class DeviceStore:
             pass
 
 
-def ChopBlob(index, blob, store, verify=True):
+def chunk_ids_known(store, blob, ends, start=0, n=None, algo=None, device_out=False):
+    """dsx_chunk_ids_known: the IDs of the chunks [start, ends[0]), [ends[0],
+    ends[1]), ... of ``blob`` (a device tensor or a ``(pointer, length)`` pair)
+    and where ``store`` holds them, in one call.  A chunk whose bytes equal a
+    stored entry's bytes gets that entry's ID by comparison; the others are
+    hashed and then looked up (make.go:223, chunkstorage.go:44-67).
+
+    ``ends`` is a host array, a device tensor of uint64, or an integer device
+    pointer with ``n``.  ``algo`` defaults to the package-global Digest and must
+    be the digest the store was filled with.  Returns ``(ids, known_off,
+    totals)``: ``ids`` as ``(n, 32)`` uint8 and ``known_off`` as uint64
+    (``OFF_NONE`` where the store lacks the ID), both exactly what dsx_chunk_ids
+    and ``store.locate`` give -- numpy arrays, or device tensors with
+    ``device_out`` (uint8 and int64) -- and the dsx_known_totals_t as a dict."""
+    ptr, length, _keep_blob = _blob_arg(blob)
+    flags = 0
+    if isinstance(ends, int):
+        if n is None:
+            raise ValueError("a device pointer to the ends needs n")
+        eptr, n, _keep_ends = ends, int(n), None
+        flags |= DSX_ENDS_DEVICE
+    elif _is_device(ends):
+        if ends.element_size() != 8 or not ends.is_contiguous():
+            raise ValueError("device ends must be contiguous uint64")
+        n = ends.numel() if n is None else int(n)
+        eptr, _keep_ends = ends.data_ptr(), ends
+        flags |= DSX_ENDS_DEVICE
+    else:
+        _keep_ends = np.ascontiguousarray(ends, dtype=np.uint64)
+        n = _keep_ends.size if n is None else int(n)
+        if n > _keep_ends.size:
+            raise ValueError(f"n = {n} but {_keep_ends.size} chunk ends")
+        eptr = _keep_ends.ctypes.data
+    if device_out:
+        import torch
+        dev = f"cuda:{store.ctx.device}"
+        ids = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+        offs = torch.empty(n, dtype=torch.int64, device=dev)
+        iptr, optr = ids.data_ptr(), offs.data_ptr()
+        flags |= _lib.DSX_OUT_DEVICE
+    else:
+        ids = np.empty((n, 32), dtype=np.uint8)
+        offs = np.empty(n, dtype=np.uint64)
+        iptr, optr = ids.ctypes.data, offs.ctypes.data
+    tot = _lib.KnownTotals()
+    with store._lock:
+        rc = lib().dsx_chunk_ids_known(store.ctx.h, store.h, ctypes.c_void_p(ptr), length, int(start),
+                                       ctypes.c_void_p(eptr), n, _digest_code(algo),
+                                       ctypes.c_void_p(iptr), ctypes.c_void_p(optr),
+                                       ctypes.byref(tot), flags)
+        if rc == _lib.DSX_E_STATE:
+            d = lib().dsx_last_error(store.ctx.h)
+            raise DsxError(rc, d.decode() if d else "")
+        _check(rc, store.ctx)
+    totals = {k: getattr(tot, k) for k, _ in _lib.KnownTotals._fields_ if k != "reserved"}
+    return ids, offs, totals
+
+
+def ChopBlob(index, blob, store, verify=True, known=False):
     """ChopFile (chop.go:14-81) for a blob in HBM: stores every chunk of
     ``index`` out of ``blob`` (a device tensor or a ``(pointer, length)``
     pair) into ``store``, a :class:`DeviceStore`.
@@ -596,8 +660,10 @@ def ChopBlob(index, blob, store, verify=True):
     the index; the first mismatch raises ``ChunkInvalid(id, sum)``.  Then comes
     one ``put``.  Unlike ChopFile, whose workers may already have stored
     earlier chunks when one turns out invalid, nothing is stored when a chunk
-    is invalid: the check of the whole blob comes before the put.  Returns the
-    put totals as a dict."""
+    is invalid: the check of the whole blob comes before the put.  With
+    ``known`` the re-hash is dsx_chunk_ids_known against ``store``: a chunk whose
+    bytes the store already holds is compared with them instead of hashed, with
+    the same IDs as the result.  Returns the put totals as a dict."""
     from .extract import _index_arrays
     from .make import chunk_ids
     ids, ends = _index_arrays(index)
@@ -605,10 +671,13 @@ def ChopBlob(index, blob, store, verify=True):
     if len(ends) and int(ends[-1]) > length:
         raise EOFError("unexpected EOF")  # (io.ReadFull on a file shorter than its index)
     if verify and len(ends):
-        with store._lock:
-            got = chunk_ids(ptr, length, ends, 0, ctx=store.ctx,
-                            algo=_digest_code(digest.Digest.Algorithm()))
-        got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
+        if known:
+            got = store.chunk_ids((ptr, length), ends, 0)[0]
+        else:
+            with store._lock:
+                got = chunk_ids(ptr, length, ends, 0, ctx=store.ctx,
+                                algo=_digest_code(digest.Digest.Algorithm()))
+            got = np.frombuffer(b"".join(got), dtype=np.uint8).reshape(-1, 32)
         bad = np.flatnonzero(np.any(got != ids, axis=1))
         if bad.size:
             i = int(bad[0])
@@ -616,20 +685,23 @@ def ChopBlob(index, blob, store, verify=True):
     return store.put((ptr, length), ids, ends, 0)
 
 
-def ChopBlobs(blobs, store, min_size, avg_size, max_size):
+def ChopBlobs(blobs, store, min_size, avg_size, max_size, known=False):
     """``desync make -s`` over many blobs in HBM: :func:`IndexFromBlobs` (one
     cut call and one hash call for all of them), then one ``put`` of every
     chunk into ``store``, a :class:`DeviceStore`.  ``blobs`` as for
     IndexFromBlobs (a list is packed first, which costs a copy).  The IDs were
-    just computed from the bytes, so nothing is re-hashed.  Returns the list of
-    indexes, one per blob (``store.counts()`` has the fill state)."""
+    just computed from the bytes, so nothing is re-hashed.  With ``known`` the
+    IDs come from dsx_chunk_ids_known against ``store`` (chunks it already holds
+    are compared, not hashed); the indexes and the store are the same either
+    way.  Returns the list of indexes, one per blob (``store.counts()`` has the
+    fill state)."""
     from .make import _index_blobs
     with store._lock:
         indexes, ptr, length, ends, ids, _keep = _index_blobs(blobs, min_size, avg_size, max_size,
-                                                              store.ctx)
+                                                              store.ctx, store if known else None)
         if len(ends):
             store.put((ptr, length), ids, ends, 0)
     return indexes
 
 
-__all__ = ["DeviceStore", "ChopBlob", "ChopBlobs", "OFF_NONE", "chunk_file_name", "chunk_id_from_filename"]
+__all__ = ["DeviceStore", "ChopBlob", "ChopBlobs", "chunk_ids_known", "OFF_NONE", "chunk_file_name", "chunk_id_from_filename"]

@@ -29,6 +29,9 @@
  *   dsx_store_*          <- a LocalStore with Uncompressed: true (store.go:21-33,
  *                           :98-99, local.go) and ChunkStorage.StoreChunk
  *                           (chunkstorage.go:44-67), for chunks resident in HBM
+ *   dsx_chunk_ids_known  <- Digest.Sum (make.go:223) and StoreChunk's HasChunk
+ *                           (chunkstorage.go:44-67) for chunks whose bytes the
+ *                           store in HBM already holds: compared, not hashed
  *   dsx_store_prune      <- PruneStore.Prune (store.go:35-39, local.go:163-202)
  *                           and RemoveChunk (local.go:69-75), compacting the
  *                           arena in place
@@ -848,6 +851,66 @@ int dsx_store_put(dsx_ctx_t *ctx, dsx_store_t *store, const void *d_blob, uint64
  * DSX_OUT_DEVICE (offs and sizes are device memory). */
 int dsx_store_locate(dsx_ctx_t *ctx, const dsx_store_t *store, const void *ids, uint64_t n,
                      uint64_t *offs, uint64_t *sizes, uint64_t *n_missing, uint32_t flags);
+
+/* ---- chunk IDs by comparison: recognise bytes the store already holds ------------
+ * dsx_chunk_ids followed by dsx_store_locate in one call -- Digest.Sum
+ * (make.go:223) and then HasChunk inside StoreChunk (chunkstorage.go:44-67) --
+ * for version N + 1 of a blob whose version N the store holds.  A chunk whose
+ * bytes equal a stored entry's bytes has that entry's ID, and store and blob lie
+ * in the same HBM: such a chunk is compared, a streaming read, instead of
+ * hashed, a serial chain.  Nothing the caller declares is trusted (no dirty
+ * ranges); chunks are matched by content, wherever they moved.  DESIGN.md 4.11
+ * has the launches.
+ * The contract is exact and does not depend on which path produced an ID:
+ *   ids[j]       (n * 32 bytes) is what dsx_chunk_ids writes;
+ *   known_off[j] (n words, may be NULL) is what dsx_store_locate writes for that
+ *                ID: the arena offset, or UINT64_MAX if the store lacks it.
+ * It assumes the store's IDs are those of its bytes under `algo`, as
+ * dsx_store_put trusts them (dsx_store_verify is the check): algo must be the
+ * digest the store was filled with, else recognised chunks carry the store's
+ * IDs and hashed chunks the other digest's.
+ * Recognition is only an accelerator.  A chunk's fingerprint -- its size, its
+ * first and last min(size, 32) bytes and, from 96 bytes on, the 32 bytes at
+ * size / 2 - 16 -- selects up to DSX_KNOWN_TRIES entries of the same size and
+ * fingerprint; the chunk's bytes are compared with each; the first equal one
+ * gives the ID and the offset.  Every other chunk is hashed and then looked up
+ * by ID.  No loop over table slots runs longer than DSX_KNOWN_PROBES: an entry
+ * or a chunk that hits a bound is hashed as well.
+ * d_blob/len/start/ends/n/algo and DSX_ENDS_DEVICE as in dsx_chunk_ids;
+ * DSX_OUT_DEVICE: ids and known_off are device memory; any other flag bit is
+ * DSX_E_INVAL.  totals (host memory, may be NULL): recognised + hashed ==
+ * chunks always.  ids, known_off and every total but untried (and what
+ * depends on which of more than DSX_KNOWN_TRIES equal fingerprints were tried)
+ * are the same on every run.
+ * Refused with DSX_E_INVAL before any device work, with a dsx_last_error text: a
+ * NULL ctx (before HIP is touched); a NULL store or ids; host ends that
+ * decrease, begin below start or end beyond len; n > 0xFFFFFFF0; an unknown
+ * digest.  A store of another context or a broken one: DSX_E_STATE, as
+ * dsx_read_ranges answers them.  n == 0: DSX_OK with zero totals.  The blob may
+ * overlap the arena: nothing is written to either.  Synchronous on the ctx
+ * stream: one host wait between resolving and hashing, one at the end; the
+ * scratch (the fingerprint table is rebuilt by every call) counts in
+ * device_bytes. */
+#define DSX_KNOWN_TILE 65536u  /* pair bytes one workgroup of the compare owns */
+#define DSX_KNOWN_TRIES 4u     /* entries compared with one chunk at most */
+#define DSX_KNOWN_PROBES 64u   /* table slots an insert or a probe visits at most */
+
+typedef struct dsx_known_totals {
+    uint64_t chunks;                     /* n */
+    uint64_t recognised, recognised_bytes; /* chunks that got their ID from an equal entry */
+    uint64_t hashed, hashed_bytes;       /* chunks the digest kernels hashed */
+    uint64_t pairs;                      /* (chunk, entry) pairs compared */
+    uint64_t compared_bytes;             /* the sum of their sizes */
+    uint64_t fp_false;                   /* pairs whose bytes differed */
+    uint64_t untried;                    /* chunks or entries that hit a bound and fell back to hashing */
+    uint64_t reserved;                   /* 0 */
+} dsx_known_totals_t;                    /* 80 bytes */
+
+int dsx_chunk_ids_known(dsx_ctx_t *ctx, const dsx_store_t *store,
+                        const void *d_blob, uint64_t len, uint64_t start,
+                        const uint64_t *ends, uint64_t n, int algo,
+                        void *ids /* n*32 */, uint64_t *known_off /* n, may be NULL */,
+                        dsx_known_totals_t *totals /* may be NULL */, uint32_t flags);
 
 /* The arena for dsx_assemble: store = *d_arena, store_len = *used, with
  * DSX_STORE_DEVICE. */
