@@ -13,6 +13,7 @@ import hashlib
 
 import numpy as np
 
+import known_ref
 import read_ref
 import store_copy_ref
 import store_prune_ref
@@ -35,7 +36,7 @@ NARROW_SEEDS = (1, 2, 3, 4)
 SCRIPTS = [("narrow", s) for s in NARROW_SEEDS] + [("wide", 0)]
 
 MUTATING = ("put", "prune", "copy", "grow", "grow_refused", "remove_chunk", "put_sealed")
-QUERIES = ("locate", "entries", "get", "read", "assemble", "verify")
+QUERIES = ("locate", "entries", "get", "read", "assemble", "verify", "known")
 FOREIGN = ("idset", "dedup", "chunk_ids", "chunk_keep")
 
 
@@ -51,8 +52,9 @@ class Pool:
     """`npool` chunks over one random blob.  Narrow: sizes i % 50 (empty ones
     among them), every 97th 4,097 bytes, three of 70,000; the IDs are the
     chunks' SHA-512/256 sums, except a few liars whose ID is the sum of other
-    bytes (a put trusts its IDs; Verify finds them).  Wide: sizes i % 16 and
-    random IDs."""
+    bytes (a put trusts its IDs; Verify finds them, and a known op recognises
+    their bytes under their ID: no other chunk has a liar's bytes).  Wide:
+    sizes i % 16 and random IDs."""
 
     def __init__(self, profile):
         p = PROFILES[profile]
@@ -84,6 +86,12 @@ class Pool:
                 else:
                     sums.append(_sum(data))
             self.ids = np.frombuffer(b"".join(sums), dtype=np.uint8).reshape(-1, 32).copy()
+            # a known op recognises a liar's bytes under the liar's ID: no other chunk may
+            # have those bytes under its own
+            by_bytes = {}
+            for i in range(n):
+                by_bytes.setdefault(raw[int(self.starts[i]):int(self.ends[i])], set()).add(sums[i])
+            assert all(len(ids) == 1 for ids in by_bytes.values()), "equal bytes under two IDs"
         self.absent = rng.integers(0, 256, (64, 32), dtype=np.uint8)  # IDs of no chunk
 
     def gather(self, picks, pad=0):
@@ -243,6 +251,18 @@ class Life:
         s = self.stores[op["store"]]
         return {"bad": [e for e, cid in enumerate(s.ids) if cid in self.pool.liars]}
 
+    def _known(self, op):
+        """dsx_chunk_ids_known: a chunk whose bytes an entry holds gets that
+        entry's ID (a liar's too), the others their hash; then the offsets by
+        ID (known_ref.StoreModel over the entries as they lie now)."""
+        s = self.stores[op["store"]]
+        blob, _, ends, start = self.pool.gather(op["picks"], op["pad"])
+        model = known_ref.StoreModel("sha512_256")
+        model.put(bytes(s.arena), s.ends, 0, ids=s.ids)
+        ids, off, rec = model.answer(blob.tobytes(), ends, start)
+        return {"ids": ids.tobytes(), "known_off": [int(o) for o in off], "recognised": int(rec),
+                "hashed": len(ends) - int(rec)}
+
     # ---- foreign calls on a context the stores use ----
     def _idset(self, op):
         ids = self.pool.ids[op["picks"]]
@@ -317,6 +337,11 @@ def _copy_op(dst, src, ids=None, ids_dev=False):
     return {"op": "copy", "store": dst, "src": src, "ids": ids, "ids_dev": bool(ids_dev)}
 
 
+def _known_op(name, picks, pad):
+    assert pad % 2 == 1
+    return {"op": "known", "store": name, "picks": np.asarray(picks, dtype=np.int64), "pad": int(pad)}
+
+
 def _with_dups(rng, picks, k):
     """k more picks, each a copy of one already there, at random places."""
     picks = list(picks)
@@ -368,6 +393,9 @@ def _query_op(rng, life, name, kind, lie=None):
         return {"op": "read", "store": name, "chunks": chunks, "ranges": ranges}
     if kind == "assemble":
         return {"op": "assemble", "store": name, "chunks": _index_chunks(rng, life, name, lie)}
+    if kind == "known":  # chunks the store holds and chunks it lacks, repeats among them
+        n = int(rng.choice([1, 17, 64, 300, 700]))
+        return _known_op(name, rng.integers(0, len(pool.ids), n), 2 * int(rng.integers(0, 8)) + 1)
     return {"op": kind, "store": name}  # entries, verify
 
 
@@ -417,12 +445,18 @@ def _prologue(rng, life, do):
     do(_copy_op(B, A))                                                        # refused: capacity
     do(_prune_op(B, _held(life.stores[B])[::2], window=WINDOW))
     do(_copy_op(B, A, _held(life.stores[A])[300:350][::-1], ids_dev=True))    # a copy after a prune
+    do(_known_op(B, range(80, 380), 3))                                       # known right after a copy
     do(_prune_op(B, _held(life.stores[B])[10:20], remove=True))               # a prune after a copy
+    do(_known_op(B, list(range(0, 900, 7)) + list(range(300, 350)), 5))       # ... after a compaction in place
     do(_query_op(rng, life, B, "assemble"))
     do(_prune_op(B, np.empty((0, 32), np.uint8)))                             # B pruned to nothing ...
     do(_foreign_op(rng, pool, "chunk_ids", 0))
     do(_put_op(B, _with_dups(rng, range(200, 260), 2), 4, ids_dev=True))      # ... and refilled
     do({"op": "grow", "store": A, "arena_bytes": 400 << 10, "max_chunks": 800})
+    # known right after a Grow, liars among the picks; then B straight after A on the
+    # context's one KnownScratch, with fewer chunks against a smaller store
+    do(_known_op(A, list(range(0, 900, 2)) + [5, 216, 427, 638, 849], 7))
+    do(_known_op(B, range(90, 330), 1))
     do({"op": "grow_refused", "store": A, "arena_bytes": 400 << 10,
         "max_chunks": life.stores[A].counts()["chunks"] - 1})
     do({"op": "put_sealed", "store": B, "src": A, "first": 10, "n": 40, "nonce_seed": 1})
@@ -567,6 +601,9 @@ def script(profile, seed):
 def periodic(life, seed, pos):
     """The queries that run on every store after every tenth op."""
     rng = np.random.default_rng([seed, pos])
+    # wide: no known.  Its pool has random IDs over chunks of 0-15 bytes, so equal bytes lie
+    # under many IDs: they fill fingerprint buckets beyond DSX_KNOWN_TRIES, and which path
+    # answers such a chunk, and with which of the IDs, is not determined (DESIGN 4.11)
     kinds = ("locate", "entries", "get", "read") if life.pool.wide else QUERIES
     return [_query_op(rng, life, name, kind) for name in life.stores for kind in kinds]
 
@@ -715,3 +752,52 @@ def conditions(profile, seed):
     c = {k: int(v) for k, v in c.items()}
     c.update(ops=len(kinds), up=sorted(up), down=sorted(down), kinds=kinds)
     return c
+
+
+def known_conditions(profile, seed):
+    """What the known ops of a script meet, counted over the script's own ops
+    on the model's walk: a known op on a store whose last change was a prune
+    with remove that removed, a copy that copied, a Grow; one on B as the
+    step straight after one on A (one context, one KnownScratch) with another
+    chunk count; and what the answers hold."""
+    pool = pool_of(profile)
+    c = dict.fromkeys(("known", "after_prune_remove", "after_copy", "after_grow", "b_after_a", "liar_ids",
+                       "recognised", "hashed", "both_in_one", "big_recognised", "big_hashed",
+                       "empty_recognised"), 0)
+    last = {}
+    prev = None
+    for pos, op, want, _states, extra in walk(profile, seed):
+        kind, name = op["op"], op.get("store")
+        if kind in MUTATING:
+            tot = want.get("totals") or {}
+            if want.get("refused"):
+                pass
+            elif kind == "prune" and tot["removed"]:
+                last[name] = "prune_remove" if op["remove"] else "prune"
+            elif kind == "remove_chunk":
+                last[name] = "prune_remove"
+            elif kind == "copy" and tot["copied"]:
+                last[name] = "copy"
+            elif kind == "grow":
+                last[name] = "grow"
+            elif kind in ("put", "put_sealed") and tot["stored"]:
+                last[name] = "put"
+        if kind == "known" and not extra:
+            ids = [want["ids"][k:k + 32] for k in range(0, len(want["ids"]), 32)]
+            sizes = pool.sizes[op["picks"]]
+            rec = np.array(want["known_off"]) != known_ref.OFF_NONE
+            assert int(rec.sum()) == want["recognised"]  # (narrow: the store holds an ID only with its bytes)
+            c["known"] += 1
+            for what in ("prune_remove", "copy", "grow"):
+                c["after_" + what] += last.get(name) == what
+            c["b_after_a"] += (name == "B" and prev is not None and prev["op"] == "known"
+                               and prev["store"] == "A" and len(prev["picks"]) != len(op["picks"]))
+            c["liar_ids"] += sum(i in pool.liars for i in ids)
+            c["recognised"] += want["recognised"]
+            c["hashed"] += want["hashed"]
+            c["both_in_one"] += want["recognised"] > 0 and want["hashed"] > 0
+            c["big_recognised"] += int((rec & (sizes == BIG)).sum())
+            c["big_hashed"] += int((~rec & (sizes == BIG)).sum())
+            c["empty_recognised"] += int((rec & (sizes == 0)).sum())
+        prev = op
+    return {k: int(v) for k, v in c.items()}

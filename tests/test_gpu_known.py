@@ -300,8 +300,24 @@ def cdc_versions():
     return a, b
 
 
-@pytest.mark.parametrize("params", [(16 << 10, 64 << 10, 256 << 10), (2 << 10, 8 << 10, 32 << 10)])
-def test_cdc_end_to_end(dctx, params):
+@pytest.mark.parametrize("params,digest", [
+    pytest.param((16 << 10, 64 << 10, 256 << 10), "sha512-256", id="params0"),
+    pytest.param((2 << 10, 8 << 10, 32 << 10), "sha512-256", id="params1"),
+    pytest.param((2 << 10, 8 << 10, 32 << 10), "sha256", id="params1-sha256")])
+def test_cdc_end_to_end(dctx, params, digest):
+    """Under either package-global digest (set_digest): the keywords pass it
+    on to the call."""
+    import desync_amd
+    before = desync_amd.digest.Digest.Algorithm()
+    desync_amd.set_digest(digest)
+    try:
+        assert desync_amd.digest.Digest.Algorithm() == digest
+        _cdc_end_to_end(dctx, params, digest)
+    finally:
+        desync_amd.set_digest(before)
+
+
+def _cdc_end_to_end(dctx, params, digest):
     import desync_amd
     from desync_amd.index import encode_to_bytes
     from desync_amd.make import chunk_ids, cut_device
@@ -315,7 +331,7 @@ def test_cdc_end_to_end(dctx, params):
         ib = desync_amd.ChopBlobs((d_a, [a.size]), known, *params, known=True)  # (an empty store: all hashed)
         assert [encode_to_bytes(i) for i in ia] == [encode_to_bytes(i) for i in ib]
         assert plain.counts() == known.counts()
-        model = known_ref.StoreModel()
+        model = known_ref.StoreModel(digest)
         ends_a = cut_device(d_a.data_ptr(), a.size, *params, ctx=dctx)
         model.put(a.tobytes(), ends_a)
         assert len(model.off) == known.counts()["chunks"]

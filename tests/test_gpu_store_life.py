@@ -4,7 +4,7 @@ copies, Grow, RemoveChunk and PutSealed on three stores in two contexts, with
 IDSet, dedup, chunk_ids and chunk_keep between them on the same scratch.  After
 every mutating call, accepted or refused, the totals or the refusal, counts(),
 every entry and the used arena must equal the model's; the queries (locate,
-entries, GetChunk, read_ranges, AssembleBlob, Verify) run where the script has
+entries, GetChunk, read_ranges, AssembleBlob, Verify, chunk_ids_known) run where the script has
 them and on every store after every tenth op.  Every malformed input is one
 the library refuses by contract: capacity, missing IDs, an index that lies to
 a read."""
@@ -218,6 +218,16 @@ class GpuBackend:
 
     def _verify(self, op):
         return {"bad": self.stores[op["store"]].verify_entries()}
+
+    def _known(self, op):
+        blob, _, ends, start = self.pool.gather(op["picks"], op["pad"])
+        ptr, _k1 = self.dev(blob)
+        earg, _k2 = self.dev(ends) if self.uploads % 2 else (ends, None)  # the ends in HBM every other time
+        ids, off, tot = self.stores[op["store"]].chunk_ids((ptr, blob.size), earg, start, n=len(ends),
+                                                           algo=_L().DSX_DIGEST_SHA512_256)
+        assert tot["chunks"] == len(ends) and tot["untried"] == 0, tot
+        return {"ids": ids.tobytes(), "known_off": [int(o) for o in off], "recognised": tot["recognised"],
+                "hashed": tot["hashed"]}
 
     # ---- foreign calls on a context the stores use ----
     def _idset(self, op):

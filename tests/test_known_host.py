@@ -5,12 +5,20 @@ The fingerprint windows and the compare's tiles are pure functions in
 desync_amd/csrc/dsx_known_geom.h; tests/known_model.cpp is a stand-alone host
 program over them, built here with the host sanitizers (it is a program of its
 own: nothing is loaded into python).
+
+The second half checks the test devices themselves: the blobs, the mask
+patterns and the marked stores test_gpu_known_paths.py runs (known_ref.py), and
+the model's lookup by bytes and then by ID against a brute-force restatement.
 """
 import ctypes
+import hashlib
 import os
 import re
 import shutil
 import subprocess
+
+import numpy as np
+import pytest
 
 import known_ref
 from desync_amd import _lib
@@ -123,3 +131,168 @@ def test_known_model(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert r.stdout.splitlines()[-1] == "known model ok: 364 sizes, 304 pair lists", r.stdout[-1000:]
+
+
+# ---- the marked store and the fixtures of test_gpu_known_paths.py ---------------------------
+SMALL_N = (1500, 2500)
+
+
+@pytest.mark.parametrize("n", SMALL_N)
+def test_path_blob(n):
+    blob = known_ref.small_blob(n)
+    chunks = list(known_ref.chunks_of(blob.raw, blob.ends))
+    assert len(chunks) == n == len(set(chunks))  # all distinct ...
+    assert len({c[:8] for c in chunks}) == n     # ... already at the number in front
+    assert all(c[:8] == i.to_bytes(8, "little") for i, c in enumerate(chunks))
+    assert [len(c) for c in chunks] == blob.sizes
+    for need in (8, 55, 56, 63, 64, 111, 112, 119, 120, 127, 128, 129, 4096, 4097):
+        assert need in known_ref.PAD_SIZES
+    assert set(known_ref.PAD_SIZES) <= set(blob.sizes) and blob.sizes.count(70000) == 1
+    assert all(z == 8 + i % 57 for i, z in enumerate(blob.sizes) if i % 4 == 3)
+    assert 400 << 10 < len(blob.raw) < 1 << 20  # about a MiB
+    for algo, name in ((0, "sha512_256"), (1, "sha256")):
+        h = blob.hashes(algo)
+        assert h.shape == (n, 32) and not h.flags.writeable
+        for i in (0, 1, known_ref.BIG_AT, n - 1):
+            assert h[i].tobytes() == hashlib.new(name, chunks[i]).digest()
+    assert blob.hashes(0) is blob.hashes("sha512-256") and not np.array_equal(blob.hashes(0), blob.hashes(1))
+
+
+PLANNED = {"every-second": lambda n: n // 2, "first-1024": lambda n: n - 1024, "last-hashed": lambda n: 1,
+           "first-hashed": lambda n: 1, "lone-63": lambda n: 1, "lone-64": lambda n: 1, "lone-65": lambda n: 1,
+           "run-64": lambda n: n - 64, "none": lambda n: n}
+
+
+@pytest.mark.parametrize("algo", [0, 1])
+@pytest.mark.parametrize("pattern", sorted(known_ref.PATTERNS))
+@pytest.mark.parametrize("n", SMALL_N)
+def test_marked_store(n, pattern, algo):
+    """The builder's claims: the planned counts, every padding length among the
+    hashed chunks, markers that are no hashes, and a path-exact answer."""
+    blob = known_ref.small_blob(n)
+    ms = known_ref.MarkedStore(blob, known_ref.PATTERNS[pattern](n), algo)
+    assert set(PLANNED) == set(known_ref.PATTERNS)
+    assert len(ms.hashed) == PLANNED[pattern](n) and len(ms.recognised) == n - len(ms.hashed)
+    assert sorted(ms.hashed.tolist() + ms.recognised.tolist()) == list(range(n))
+    if len(ms.hashed) >= 100:
+        assert {blob.sizes[i] for i in ms.hashed} >= set(known_ref.PAD_SIZES)
+    else:
+        assert len(ms.hashed) == 1
+    assert {"lone-63": [63], "lone-64": [64], "lone-65": [65], "last-hashed": [n - 1],
+            "first-hashed": [0]}.get(pattern, ms.hashed.tolist()) == ms.hashed.tolist()
+    if pattern == "first-1024":
+        # the grid is sized by the hashed chunks: at 1,500 every static lane starts on an
+        # untaken chunk, at 2,500 the first 1,024 of 1,536 do
+        lanes = 256 * -(-len(ms.hashed) // 256)
+        assert ms.hashed.min() == 1024 and (lanes <= 1024) == (n == 1500) and lanes <= 1536
+    assert len(ms.lied) == min(3, len(ms.hashed)) and set(ms.lied) <= set(ms.hashed.tolist())
+    # no marker is a hash, of either digest, of a chunk or of an entry
+    hashes = {r.tobytes() for a in (0, 1) for r in blob.hashes(a)}
+    hashes |= {known_ref.digest(c, a) for a in (0, 1) for c in known_ref.chunks_of(ms.raw, ms.ends)}
+    markers = {known_ref.marker(i) for i in range(n + 3000)} | {known_ref.marker(1 << 40)}
+    assert len(markers) == n + 3001 and not markers & hashes
+    stored = [r.tobytes() for r in ms.ids]
+    assert sum(i in markers for i in stored) == len(stored) - len(ms.lied)
+    assert len(stored) == 1 + len(ms.recognised) + known_ref.N_OTHERS + len(ms.lied)
+    # the liars: the hash of a hashed chunk over other bytes of another size
+    ends = [0] + ms.ends.tolist()
+    for x in ms.lied:
+        e = stored.index(blob.hashes(algo)[x].tobytes())
+        assert ends[e + 1] - ends[e] == blob.sizes[x] + 1
+    ids, off = ms.want()
+    for i in ms.recognised[:50]:
+        e = stored.index(known_ref.marker(int(i)))
+        assert ids[i].tobytes() == stored[e] and off[i] == ends[e]
+        assert ms.raw[ends[e]:ends[e + 1]] == blob.chunk(i)
+    for i in ms.hashed[:50]:
+        assert ids[i].tobytes() == known_ref.digest(blob.chunk(i), algo)
+        assert (off[i] != known_ref.OFF_NONE) == (int(i) in ms.lied)
+    assert ends[1] == 13  # the junk entry: no recognised chunk at offset 0
+
+
+def test_big_plan():
+    """The plan of test_big at 256 CUs, on a tenth of the chunks."""
+    lanes = 256 * 4 * 256
+    n = -(-(lanes + 16384) * 8 // 7) + 8
+    assert 318000 < n < 321000 and n // 8 <= len(range(3, n, 8)) <= n // 8 + 1
+    assert n - len(range(3, n, 8)) >= lanes + 16384 > 256 * 64 * 2
+    assert 11_000_000 < sum(known_ref.tiny_sizes(n)) < 13_000_000  # about 12 MB
+    m = n // 10
+    ms = known_ref.MarkedStore(known_ref.tiny_blob(m), range(3, m, 8), 1, check_sizes=False)
+    ids, off = ms.want()
+    assert ids.shape == (m, 32) and int((off != known_ref.OFF_NONE).sum()) == len(range(3, m, 8)) + 3
+
+
+def brute_force(entries, chunks, algo):
+    """The model restated: a linear scan over the entries comparing bytes,
+    then one comparing IDs."""
+    ids, offs, rec = [], [], 0
+    for c in chunks:
+        for i, data, _ in entries:
+            if data == c:
+                rec += 1
+                break
+        else:
+            i = hashlib.new(algo, c).digest()
+        ids.append(i)
+        for j, _, o in entries:
+            if j == i:
+                offs.append(o)
+                break
+        else:
+            offs.append(known_ref.OFF_NONE)
+    return ids, offs, rec
+
+
+def test_model_against_brute_force():
+    """200 random small cases: honest, marked and lying entries, repeated IDs
+    in a put (the first occurrence is stored), chunks the store holds, lacks,
+    and holds only by ID; both digests; a start behind a pad."""
+    rng = np.random.default_rng(411)
+    seen = {"marked": 0, "by_id": 0, "hashed": 0, "repeat": 0}
+    for case in range(200):
+        algo = known_ref.ALGOS[case % 2]
+        alphabet = [rng.integers(0, 4, int(rng.integers(0, 4)), dtype=np.uint8).tobytes() + bytes([k])
+                    for k in range(24)] + [b""]
+        model, entries, used, held = known_ref.StoreModel(algo), [], 0, {}
+        for _ in range(int(rng.integers(0, 3))):  # puts
+            picks = rng.integers(0, 18, int(rng.integers(0, 12)))
+            data = [alphabet[k] for k in picks]
+            ids = []
+            for k, c in zip(picks, data):
+                r = rng.random()
+                if c in held:  # equal bytes keep their ID: a store never holds them under two
+                    ids.append(held[c])
+                    seen["repeat"] += 1
+                elif r < 0.3:
+                    ids.append(known_ref.marker(int(k)))
+                elif r < 0.45:  # a liar: the hash of a chunk the store will not hold
+                    ids.append(hashlib.new(algo, alphabet[18 + int(k) % 6]).digest())
+                else:
+                    ids.append(hashlib.new(algo, c).digest())
+                if ids[-1] in {i for i, _, _ in entries} | set(ids[:-1]) and c not in held:
+                    ids[-1] = known_ref.marker(1000 + len(entries) + len(ids))  # (an ID names one entry)
+                held.setdefault(c, ids[-1])
+                if ids[-1] not in {i for i, _, _ in entries}:
+                    entries.append((ids[-1], c, used))
+                    used += len(c)
+            pad = int(rng.integers(0, 5))
+            raw = bytes(pad) + b"".join(data)
+            ends = pad + np.cumsum([len(c) for c in data], dtype=np.int64)
+            arg = None if all(i == hashlib.new(algo, c).digest() for i, c in zip(ids, data)) else \
+                (known_ref.id_rows(ids) if rng.random() < 0.5 else ids)
+            model.put(raw, ends, pad, ids=arg)
+        assert model.used == used and list(model.off.items()) == [(i, o) for i, _, o in entries]
+        chunks = [alphabet[k] for k in rng.integers(0, 25, int(rng.integers(0, 30)))]
+        pad = int(rng.integers(0, 5))
+        raw = bytes(pad) + b"".join(chunks)
+        ends = pad + np.cumsum([len(c) for c in chunks], dtype=np.int64)
+        ids, offs, rec = model.answer(raw, ends, pad)
+        want_ids, want_offs, want_rec = brute_force(entries, chunks, algo)
+        assert [r.tobytes() for r in ids] == want_ids and offs.tolist() == want_offs and rec == want_rec
+        assert ids.shape == (len(chunks), 32) and offs.dtype == np.uint64
+        markers = {known_ref.marker(k) for k in range(1100)}
+        seen["marked"] += sum(i in markers for i in want_ids)
+        seen["by_id"] += sum(o != known_ref.OFF_NONE and c not in held for o, c in zip(want_offs, chunks))
+        seen["hashed"] += len(chunks) - rec
+    assert min(seen.values()) >= 20, seen

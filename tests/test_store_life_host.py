@@ -2,7 +2,9 @@
 committed (profile, seed) script must contain the rare sequences the GPU test
 exists for, the generator must be deterministic, and the driver's comparison
 must notice a store that is wrong: three deliberately broken models are each
-caught by every narrow script, at the first op they affect."""
+caught by every narrow script, at the first op they affect.  The known op
+(dsx_chunk_ids_known) must come where the store has just lived: after a
+compaction, a copy, a Grow, and on B straight after A."""
 import numpy as np
 import pytest
 
@@ -81,6 +83,57 @@ def test_narrow_conditions(profile, seed):
         assert {op[key] for op in ops if op["op"] == "prune"} == both, key
     assert any(op["op"] == "copy" and op["ids"] is None for op in ops)
     assert any(op["op"] == "copy" and op["ids"] is not None for op in ops)
+
+
+def test_liars_share_no_bytes():
+    """A known op recognises a liar's bytes under the liar's ID, so no other
+    pool chunk may have those bytes (Pool.__init__ asserts it over all pairs;
+    here by size: a liar shares its size with 17 others at the most, all
+    random, and none is empty)."""
+    pool = life_ref.pool_of("narrow")
+    liars = [i for i in range(900) if i % 211 == 5]
+    assert len(liars) == 5 and {pool.ids[i].tobytes() for i in liars} == pool.liars
+    for i in liars:
+        assert pool.sizes[i] >= 5
+        assert all(pool.data(j) != pool.data(i) for j in range(900) if j != i)
+
+
+@pytest.mark.parametrize("profile,seed", NARROW)
+def test_known_conditions(profile, seed):
+    """dsx_chunk_ids_known inside the store's life: right after an in-place
+    compaction, a copy and a Grow of its store, on B straight after A (the two
+    share a context's KnownScratch), with a liar's bytes recognised under the
+    liar's ID, and chunks of every kind on either path."""
+    c = life_ref.known_conditions(profile, seed)
+    assert c["known"] >= 4, c
+    assert c["after_prune_remove"] >= 1 and c["after_copy"] >= 1 and c["after_grow"] >= 1, c
+    assert c["b_after_a"] >= 1, c
+    assert c["liar_ids"] >= 3, c
+    assert c["recognised"] >= 300 and c["hashed"] >= 300 and c["both_in_one"] >= 4, c
+    assert c["big_recognised"] >= 1 and c["big_hashed"] >= 1 and c["empty_recognised"] >= 1, c
+    # the periodic queries run it on every store, and never on the wide pool
+    extras = [op for _, op, _, _, extra in life_ref.walk(profile, seed) if extra and op["op"] == "known"]
+    assert len(extras) == 12 * 3 and {op["store"] for op in extras} == {"A", "B", "C"}
+    assert all(op["pad"] % 2 == 1 for op in script(profile, seed) if op["op"] == "known")
+    assert "known" in life_ref.QUERIES
+    assert not any(op["op"] == "known" for _, op, _, _, _ in life_ref.walk("wide", 0))
+
+
+def test_known_model_answers_by_bytes_then_by_id():
+    """The op on a store with a liar: the chunk with the liar's bytes carries
+    the liar's ID and its offset; a chunk the store lacks its hash and
+    OFF_NONE; an empty chunk is recognised once the store holds one."""
+    life = Life("narrow")
+    pool = life.pool
+    life.apply(life_ref._put_op("A", [7, 5, 0, 9], 3))
+    res = life.apply(life_ref._known_op("A", [9, 5, 50, 11, 5, 7], 1))
+    ids = [res["ids"][k:k + 32] for k in range(0, 192, 32)]
+    assert ids[1] == ids[4] == pool.ids[5].tobytes() != life_ref._sum(pool.data(5))
+    assert ids[1] in pool.liars
+    assert ids[0] == life_ref._sum(pool.data(9)) and ids[3] == life_ref._sum(pool.data(11))
+    assert ids[2] == life_ref._sum(b"") == pool.ids[0].tobytes()  # chunk 50 is empty as chunk 0 is
+    assert res["known_off"] == [7 + 5, 7, 7 + 5, life_ref.store_ref.OFF_NONE, 7, 0]
+    assert (res["recognised"], res["hashed"]) == (5, 1)
 
 
 def test_wide_conditions():
