@@ -222,7 +222,7 @@ extern "C" int dsx_ctx_create(int device, dsx_ctx_t** out) {
     }
   }
 #endif
-  // coherent, like h_ring: the tail feeder (dsx_index.cpp) and dsx_progress
+  // coherent, like h_ring: the tail feeder (dsx_hosttail.cpp) and dsx_progress
   // poll it while the stitch publishes into it mid-call
   CREATE_STEP(hipHostMalloc((void**)&c->h_state, sizeof(HostState), hipHostMallocCoherent));
   // coherent: dsx_result polls the seq the GPU publishes here

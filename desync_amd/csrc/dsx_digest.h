@@ -29,7 +29,7 @@ struct DigestArgs {
   // chunk order[k]; null: index order
   const uint32_t* order;
   // chunks longer than this get no ID here (0: none): the index pipeline
-  // hashes them on the host (dsx_index.cpp, host tail)
+  // hashes them on the host (dsx_hosttail.cpp, the host tail)
   uint64_t skip_above;
   // one byte per chunk (null: every chunk): a chunk whose byte is 0 gets no ID
   // here and is left out of the longest-first order (dsx_known.hip hashes only

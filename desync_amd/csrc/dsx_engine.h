@@ -15,6 +15,7 @@
 #include "../../include/dsx.h"
 #include "dsx_common.h"
 #include "dsx_digest.h"
+#include "dsx_index_plan.h"
 #include "dsx_many.h"
 #include "dsx_many_plan.h"
 #include "dsx_scan_geom.h"
@@ -327,7 +328,7 @@ struct dsx_ctx {
   // digest on `stream`); lowest priority: the runtime's
   // low-priority pool of GPU_MAX_HW_QUEUES (4) HSA queues holds exactly these,
   // none shared with `stream` or `copy_stream` (tools/queue_probe.hip)
-  static constexpr int kIdxSide = 4;
+  static constexpr int kIdxSide = dsx_host::kIdxSide;  // (dsx_index_plan.h: the schedules count them)
   hipStream_t idx_side[kIdxSide] = {};
   DevBuf<uint32_t> idx_side_q;
   hipEvent_t q_ev[kQueueDepth] = {};

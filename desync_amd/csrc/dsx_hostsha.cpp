@@ -1,6 +1,6 @@
 // dsx_hostsha.cpp -- SHA-512/256 chunk IDs on the host (Digest.Sum,
 // digest.go:22; FIPS 180-4 sec. 6.4 and 5.3.6.2) for the index pipeline's
-// longest chunks at the end of a file (dsx_index.cpp): a GPU
+// longest chunks at the end of a file (dsx_hosttail.cpp): a GPU
 // lane hashes one SHA-512 block per ~5 us, so the last window's digest lasts
 // its longest chunk's chain (~10 ms for 256 KiB); a host core hashes 8 chunks
 // at once in the qword lanes of AVX-512 registers at ~1-2 GB/s.

@@ -1,6 +1,6 @@
 """The one-window share schedule of IndexFromFile on the GPU: every chunk ID
 is hashed exactly once by the GPU's shares, the tail feeder or the digest
-after the read (dsx_index.cpp index_schedule), at the geometries where the
+after the read (dsx_index_plan.h index_schedule), at the geometries where the
 three once disagreed.
 
 Until round 7 a planned share that no scan point below the end of the file
@@ -28,8 +28,10 @@ Diagnostic library (one child process, DSX_LIB_PATH): the same shapes at
 DSX_FEED_MID, DSX_FINE_TAIL=0 and DSX_FEED_THREADS=28.
 
 stats.host_tail_chunks must equal the count the schedule's per-segment cuts
-give on the reference chain, for dsx_index_fd and dsx_index_host.  (Not for
-dsx_ids_*: run_ids plans its last cut from this host's measured SHA rate.)
+give on the reference chain, for dsx_index_fd and dsx_index_host; in the
+diagnostic child also for dsx_ids_fd and dsx_ids_host, under run_ids's own
+schedule (ids_schedule) at this process's measured SHA rate
+(dsx_diag_host_ns_per_byte), which its last cut is planned from.
 """
 import concurrent.futures as cf
 import hashlib
@@ -86,11 +88,13 @@ def _first_mismatch(got, want, ref):
     return None
 
 
-def _check_four(ctx, data, path, primer, primer_path, ref, want, sched, algo="sha512-256", log=None):
+def _check_four(ctx, data, path, primer, primer_path, ref, want, sched, algo="sha512-256", log=None,
+                ids_want=None):
     """dsx_index_fd, dsx_index_host, dsx_ids_fd and dsx_ids_host on `ctx`,
     each after the same entry point over the primer: the cut list is the
     reference's, every ID hashlib's, and (sched given) the host hashed exactly
-    the chunks above their segment's cut."""
+    the chunks above their segment's cut; (ids_want given) dsx_ids_* had the
+    host hash exactly that many chunks."""
     import desync_amd
     n_want = None if sched is None else S.host_chunks(sched, ref)
     if sched is not None:
@@ -137,6 +141,11 @@ def _check_four(ctx, data, path, primer, primer_path, ref, want, sched, algo="sh
              lambda: desync_amd.ids_host(data, 0, ref, algo=algo, ctx=ctx))):
         prime()
         check_ids(name, call())
+        n_host = ctx.stats().host_tail_chunks
+        if log is not None:
+            log.append(f"{name} host {n_host} (want {ids_want})")
+        if ids_want is not None:
+            assert n_host == ids_want, (name, n_host, ids_want)
 
 
 # ------------------------------------------------------------ product library
@@ -307,10 +316,22 @@ def _main():
                                 for i in range(ref.size)]
                     by_algo[algo] = (ref, want)
                 ref, want = by_algo[algo]
+                # run_ids's schedule of the reference list under this
+                # environment, at this process's SHA rate (None: a chunk ends
+                # exactly where a share lands, or no AVX-512)
+                ids_want = None
+                if avx or algo == "sha256":
+                    isched = S.ids_schedule(lib, 0, ref, slot or 32 << 20, window or 1 << 30, THREADS,
+                                            host_tail=-1, tail_on=algo == "sha512-256",
+                                            host_ns=lib.dsx_diag_host_ns_per_byte())
+                    assert S.ids_violations(isched, 0, ref, THREADS, -1, algo == "sha512-256",
+                                            lib.dsx_diag_host_ns_per_byte()) == []
+                    ids_want = S.ids_host_chunks(isched, 0, ref)
                 ctx = _lib.Context(0)
                 try:
                     _check_four(ctx, data, paths[0], primer, paths[1], ref, want,
-                                sched if avx or algo == "sha256" else None, algo=algo, log=log)
+                                sched if avx or algo == "sha256" else None, algo=algo, log=log,
+                                ids_want=ids_want)
                 finally:
                     ctx.close()
                 print(f"case {name}: ok {time.perf_counter() - t0:.2f} s; " + "; ".join(log), flush=True)

@@ -436,7 +436,7 @@ def _diag_lib():
     (1 << 30, 1, 131072, 90112, [(1 << 29, 262144)]),
 ])
 def test_index_share_plan(length, threads, fcut, fcut_end, shares):
-    """The one-window IndexFromFile plan (dsx_index.cpp plan_shares,
+    """The one-window IndexFromFile plan (dsx_index_plan.h plan_shares,
     feed_cut_for, share_end_cut): the feeder's cut from its threads, the GPU's
     shares at 1/2, 3/4, ... with cut = the read time left / 45 ns per byte,
     stopping below 1.5 x the feeder's cut, and 11/16 of it after them."""
@@ -503,7 +503,7 @@ def _sweep_lengths():
 @pytest.mark.parametrize("window", _SWEEP_WINDOWS)
 @pytest.mark.parametrize("slot", _SWEEP_SLOTS)
 def test_index_schedule_sweep(slot, window):
-    """The schedule run_index executes (dsx_index.cpp index_schedule, through
+    """The schedule run_index executes (dsx_index_plan.h index_schedule, through
     dsx_diag_index_schedule) over lengths from 1 B to 5 GiB x 1, 12 and 28
     feeder threads, per read slot and HBM window (80 MiB windows put the
     shares into the last of several): the segments tile the last window; in
@@ -573,6 +573,125 @@ def test_index_schedule_named(name, length, slot, threads, scan, fire, segs):
         assert s["scan"] == scan
     assert [f for _, _, f in s["shares"]] == fire
     assert s["segs"] == segs
+
+
+def test_index_plan_model(tmp_path):
+    """dsx_index_plan.h alone, under the host sanitizers: index_schedule over
+    lengths, slots, windows, threads and host-tail settings, ids_schedule over
+    seeded lists of 1-5 GiB and the awkward ones; a broken invariant is a
+    non-zero exit (tests/index_plan_model.cpp)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "index_plan_model")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-I" + os.path.join(repo, "desync_amd", "csrc"),
+           os.path.join(repo, "tests", "index_plan_model.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.splitlines()[-1].startswith("index plan model ok: "), r.stdout[-1000:]
+
+
+# --------------------------------------------- run_ids's schedule (no GPU)
+_KiB, _GiB = 1 << 10, 1 << 30
+
+
+def _ids_list(seed, start, total, lo=16 * _KiB, hi=256 * _KiB, zeros=0.0):
+    """(start, ends): seeded chunk lengths in [lo, hi], skewed to the short
+    side, about `zeros` of them empty, `total` bytes from `start`; no bytes."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    n = int(total // lo) + 2
+    lens = lo + ((hi - lo) * rng.random(n) ** 2).astype(np.int64)
+    lens[rng.random(n) < zeros] = 0
+    ends = np.cumsum(lens)
+    ends = ends[:int(np.searchsorted(ends, total)) + 1]
+    ends[-1] = total
+    return start, (ends + start).astype(np.uint64)
+
+
+def _ids_lists():
+    import numpy as np
+    big = [("1GiB", _ids_list(1, 0, _GiB)),
+           ("1.34GiB-start", _ids_list(2, 4321, _GiB + (352 << 20) + 4321)),
+           ("3GiB", _ids_list(3, 0, 3 * _GiB - 7)),
+           ("5GiB-zeros", _ids_list(4, 77, 5 * _GiB, zeros=0.02))]
+    # test_gpu_index.py::test_ids_fd_many_windows' kinds: a start, empty
+    # chunks, a chunk longer than the window, one chunk, none
+    small = [("start-zeros", _ids_list(5, 12345, (9 << 20) + 17, 1, 64 * _KiB, zeros=0.1)),
+             ("long-chunks", _ids_list(6, 777, 6 << 20, 3 << 19, 3 << 20)),
+             ("one", (5, np.array([5 + 100 * _KiB], np.uint64))),
+             ("none", (99, np.array([], np.uint64))),
+             ("no-bytes", (4096, np.array([4096] * 3, np.uint64))),
+             ("ends-at-0-and-window-end", (0, np.array([0, 0, 2 << 20, 2 << 20, (2 << 20) + 1], np.uint64)))]
+    return big, small
+
+
+@pytest.mark.parametrize("slot", [256 << 10, 32 << 20, 288 << 20, 1 << 30])
+def test_ids_schedule_sweep(slot):
+    """The schedule run_ids executes (dsx_index_plan.h ids_schedule, through
+    dsx_diag_ids_schedule) over lists given as ends only -- 1-5 GiB of 16/64/
+    256 KiB chunks, so that the product constants make shares fire, and the
+    awkward lists through 1 MiB windows -- x 1, 12 and 28 threads x host tail
+    auto, off and forced x a host of 0.38 and 1.52 ns per byte: the window
+    ranges tile the list, every chunk ending in its window with its bytes
+    kept; the segments tile the last window's chunks, the host's cut being
+    the GPU's skip_above in each; the shares land in whole pieces below the
+    end, their chunks landed by then; the last cut is the lowest multiple of
+    4096 whose host bytes fit the budget (brute force); and every chunk of
+    the last window has exactly one taker.  A schedule that breaks one of
+    these returns IDs hashed by nobody (or twice) with return code 0."""
+    S = _index_sched()
+    lib = _diag_lib()
+    big, small = _ids_lists()
+    cases = [(name, li, w) for name, li in big for w in (1 << 30, 80 << 20)]
+    cases += [(name, li, w) for name, li in small for w in (1 << 20, 1 << 30)]
+    bad, with_shares, low_cut, multi = [], 0, 0, 0
+    for name, (start, ends), window in cases:
+        for threads in (1, 12, 28):
+            for host_tail in (-1, 0, 40000):
+                for host_ns in (0.38, 1.52):
+                    for tail_on in ((True, False) if host_tail < 0 and host_ns < 1 else (host_tail != 0,)):
+                        s = S.ids_schedule(lib, start, ends, slot, window, threads, host_tail, tail_on, host_ns)
+                        v = S.ids_violations(s, start, ends, threads, host_tail, tail_on, host_ns)
+                        if v:
+                            bad.append((name, window, threads, host_tail, host_ns, tail_on, v))
+                        with_shares += bool(s["shares"])
+                        low_cut += bool(s["shares"]) and s["end_cut"] < s["early_cut"]
+                        multi += s["nwin"] > 1
+    assert not bad, f"{len(bad)} schedules: " + "; ".join(f"{b[:-1]}: {b[-1][0]}" for b in bad[:8])
+    assert multi > 20  # (one and several windows)
+    if slot <= 32 << 20:  # (the sweep reaches the shares and the budget search at all)
+        assert with_shares > 10 and low_cut > 5, (with_shares, low_cut)
+
+
+def test_ids_schedule_named():
+    """One schedule pinned value by value: 1 GiB + 352 MiB + 4321 B of seeded
+    16/64/256 KiB chunks from offset 4321 through the default slot and window
+    at 12 threads (two windows: the shares are the last one's), and the count
+    of chunks the host hashes under it."""
+    S = _index_sched()
+    lib = _diag_lib()
+    start, ends = _ids_list(2, 4321, _GiB + (352 << 20) + 4321)
+    s = S.ids_schedule(lib, start, ends, 32 << 20, 1 << 30, 12, host_ns=0.38)
+    assert S.ids_violations(s, start, ends, 12, host_ns=0.38) == []
+    assert (s["pre"], s["piece"], s["W"], s["nwin"], s["early_cut"]) == (262144, 32 << 20, 1 << 30, 2, 65536)
+    assert s["L"] == _GiB + (352 << 20) + 4321 and s["win_i1"][-1] == ends.size
+    # the last window is 352 MiB + 4321 B: too short for a share at 12 threads
+    # (the first cut, 352 MiB / 2 / 45 / 45 B = 91 KiB, is below 2 x 64 KiB)
+    assert s["shares"] == [] and s["segs"] == [(s["i_last"], ends.size, 65536, 65536)]
+    assert S.ids_host_chunks(s, start, ends) == int(((ends[s["i_last"]:] - ends[s["i_last"] - 1:-1]) > 65536).sum())
+    # at 28 threads the cut is 28 KiB and two shares fit (as in run_index:
+    # cuts 90112 and 45056), landing at whole pieces after 1/2 and 3/4
+    s = S.ids_schedule(lib, start, ends, 32 << 20, 1 << 30, 28, host_ns=0.38)
+    assert S.ids_violations(s, start, ends, 28, host_ns=0.38) == []
+    assert [(a, b) for a, b, _ in s["shares"]] == [(_GiB + (192 << 20), 90112), (_GiB + (288 << 20), 45056)]
+    assert [q[2:] for q in s["segs"][:2]] == [(90112, 90112), (45056, 45056)]
+    assert s["segs"][2][2] == s["segs"][2][3] == s["end_cut"] and s["end_cut"] % 4096 == 0
 
 
 _ENV_CHILD = r"""

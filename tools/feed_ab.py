@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""In-process A/B of IndexFromFile's one-window tail feeder (dsx_index.cpp,
+"""In-process A/B of IndexFromFile's one-window tail feeder (dsx_index.cpp, dsx_hosttail.cpp,
 TailFeeder): a 1 GiB page-cache file, `dsx_index_fd` under several feeder
 settings and `dsx_cut_fd` (the same read without IDs), the cases alternating
 call by call so that the box's drift in page-cache read speed falls on all of
