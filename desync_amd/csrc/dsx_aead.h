@@ -27,6 +27,3 @@ struct AeadScratch {
   DevBuf<uint8_t> nonces;           // seal: n * 24
   DevBuf<uint8_t> flag;             // open: bad[i]; selftest: the tag
 };
-
-uint64_t aead_device_bytes(const dsx_ctx* c);
-void aead_release(dsx_ctx* c);

@@ -501,17 +501,6 @@ __global__ __launch_bounds__(kAeadThreads) void aead_scrub_kernel(AeadArgs a, u6
 
 using namespace dsx;
 
-uint64_t aead_device_bytes(const dsx_ctx* c) {
-  const AeadScratch& t = c->aead;
-  return t.key.n + t.rctx.n * 4 + t.slots.n * 4 + t.ends.n * 8 + t.offs.n * 8 + t.nonces.n + t.flag.n;
-}
-
-void aead_release(dsx_ctx* c) {
-  AeadScratch& t = c->aead;
-  t.key.release(), t.rctx.release(), t.slots.release(), t.ends.release(), t.offs.release();
-  t.nonces.release(), t.flag.release();
-}
-
 namespace {
 
 // Clears what depends on the key.  Runs on every path out of a call that has

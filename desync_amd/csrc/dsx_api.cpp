@@ -26,9 +26,6 @@ using namespace dsx;
 static_assert(sizeof(dsx_seam_t) == 7 * 8 + 4 * 4 + 8 * (DSX_SEAM_MAX_CANDS + DSX_SEAM_MAX_CUTS),
               "dsx_seam_t layout");
 
-static void release_kept(dsx_ctx* c);
-
-
 int set_hip_err(dsx_ctx* c, hipError_t e, const char* what) {
   char buf[256];
   snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -114,7 +111,7 @@ extern "C" int dsx_ctx_create(int device, dsx_ctx_t** out) {
   c->device = device;
 #define CREATE_STEP(expr)                                                              \
   do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
+    const hipError_t e_ = static_cast<hipError_t>(expr);                               \
     if (e_ != hipSuccess) {                                                            \
       snprintf(g_create_err, sizeof g_create_err, "%s: %s (%d)", #expr,                \
                hipGetErrorString(e_), (int)e_);                                        \
@@ -236,10 +233,10 @@ extern "C" int dsx_ctx_create(int device, dsx_ctx_t** out) {
   CREATE_STEP(hipHostMalloc((void**)&c->h_tasks, dsx_ctx::kTaskRing * sizeof(TaskArgs), hipHostMallocCoherent));
 #endif
   memset(c->h_state, 0, sizeof(HostState));
-  CREATE_STEP(c->state.ensure(1));
+  CREATE_STEP(c->state.ensure(c->mem, 1));
   // [0..1] overflow (piece parity); [32 + 256*parity + 32*x] the scan's work
   // queue counter x = 0..7 (one per XCD, each on its own 128-B line)
-  CREATE_STEP(c->overflow.ensure(kQueueWords));
+  CREATE_STEP(c->overflow.ensure(c->mem, kQueueWords));
   CREATE_STEP(hipMemset(c->overflow.p, 0, kQueueWords * sizeof(uint32_t)));
   CREATE_STEP(hipMemset(c->state.p, 0, sizeof(DevState)));
 #undef CREATE_STEP
@@ -253,25 +250,13 @@ extern "C" int dsx_ctx_destroy(dsx_ctx_t* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (c->scan_stream && c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
-  c->region_cnt.release(); c->region_list.release(); c->overflow.release(); c->rep_cnt.release(); c->rep_from.release();
-  c->region_cnt2.release(); c->region_list2.release();
-  c->flag_list.release(); c->lane_slot.release(); c->seg_info.release(); c->stage.release();
-  c->dg_ends.release(); c->dg_ids.release(); c->dg_queue.release();
-  c->dg_order.release(); c->dg_cls.release();
-  c->rep.release(); c->out_off.release(); c->out.release(); c->state.release();
-  c->seg_info2.release(); c->stage2.release(); c->spec.release(); c->spec2.release();
-  release_kept(c);
-  c->zero_word.release();
-  c->d_seam.release(); c->d_all.release(); c->d_ext.release(); c->d_info.release(); c->d_emit.release();
   if (c->h_res) (void)hipHostFree(c->h_res);
   if (c->h_tasks) (void)hipHostFree(c->h_tasks);
   index_release(c);
   stream_release(c);
   store_release(c);
-  aead_release(c);
-  known_release(c);
-  many_release(c);
   idset_release(c);
+  c->mem.release_all();  // every device buffer still held, whoever's it was
   if (c->h_state) (void)hipHostFree(c->h_state);
   if (c->h_ring) (void)hipHostFree(c->h_ring);
   for (uint32_t i = 0; i < kQueueDepth; ++i)
@@ -345,31 +330,14 @@ extern "C" int dsx_copy(dsx_ctx_t* c, void* dst, const void* src, uint64_t n) {
   return DSX_OK;
 }
 
-// Every device buffer a context holds (all of them are DevBufs, dsx_engine.h;
-// tests/test_gpu_multiproc.py checks the sum against hipMemGetInfo).
-static uint64_t ctx_device_bytes(const dsx_ctx* c) {
-  uint64_t b = 0;
-  auto add = [&](const auto& d) { b += d.n * sizeof(*d.p); };
-  add(c->trace);
-  add(c->region_cnt), add(c->region_list), add(c->overflow), add(c->rep_cnt), add(c->rep_from);
-  add(c->flag_list), add(c->region_cnt2), add(c->region_list2), add(c->lane_slot);
-  add(c->seg_info), add(c->stage), add(c->rep), add(c->out_off), add(c->out);
-  add(c->dg_ends), add(c->dg_ids), add(c->dg_queue), add(c->dg_order), add(c->dg_cls);
-  add(c->state), add(c->seg_info2), add(c->stage2), add(c->spec), add(c->spec2);
-  for (int i = 0; i < dsx_ctx::Stream::kSlots; ++i)
-    add(c->st.dbuf[i]), add(c->st.dout[i]), add(c->st.dids[i]);
-  add(c->st.rng), add(c->st.dq);
-  for (const auto& k : c->sh.kept) add(k.cnt), add(k.list);
-  add(c->d_seam), add(c->d_all), add(c->zero_word), add(c->d_ext), add(c->d_info), add(c->d_emit);
-  add(c->stamp_ring), add(c->idx_win[0]), add(c->idx_win[1]), add(c->idx_snap);
-  return b + idset_device_bytes(c) + store_device_bytes(c) + aead_device_bytes(c) + many_device_bytes(c) +
-         known_device_bytes(c);
-}
-
+// device_bytes: the total of the context's ledger (dsx_devmem.h), which every
+// device allocation of the library goes through: n * sizeof(T) of each live
+// DevBuf, the live stores' and ID sets' among them
+// (tests/test_gpu_multiproc.py checks it against hipMemGetInfo).
 extern "C" int dsx_get_stats(dsx_ctx_t* c, dsx_stats_t* out) {
   if (!c || !out) return DSX_E_INVAL;
   *out = c->stats;
-  out->device_bytes = ctx_device_bytes(c);
+  out->device_bytes = c->mem.bytes();
   return DSX_OK;
 }
 
@@ -729,7 +697,7 @@ int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream
   const bool own = stream == nullptr || serial;
   if (!stream) stream = c->stream;
   if (!queue) {
-    HIPCHK(c, c->dg_queue.ensure(1));
+    HIPCHK(c, c->dg_queue.ensure(c->mem, 1));
     queue = c->dg_queue.p;
   }
   // split producer/consumer kernel: one workgroup (producer + consumer wave)
@@ -783,7 +751,7 @@ int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream
   // are of one size, so no lane idles behind a longer neighbour
   if (own && c->digest_lpt && max_n >= 8u * kDigestThreads && max_n < (1ull << 32)) {
     HIPCHK(c, grow(c, c->dg_order, max_n));
-    HIPCHK(c, c->dg_cls.ensure(2 * kSizeClasses));
+    HIPCHK(c, c->dg_cls.ensure(c->mem, 2 * kSizeClasses));
     HIPCHK(c, hipMemsetAsync(c->dg_cls.p, 0, kSizeClasses * sizeof(uint32_t), stream));
     // (a take mask: the order lists the chunks taken and ends at the first 0xFFFFFFFF)
     if (da.take) HIPCHK(c, hipMemsetAsync(c->dg_order.p, 0xFF, max_n * sizeof(uint32_t), stream));
@@ -877,7 +845,7 @@ extern "C" int dsx_selftest_boundary(dsx_ctx_t* c, const dsx_params_t* p, int mo
   const uint32_t d = p->discriminator;
   if (mode > 2 || (mode == 2 && (d & (d - 1u)) == 0)) return DSX_E_INVAL;  // MODE 2 needs dodd > 1
   DevBuf<unsigned long long> m;
-  HIPCHK(c, m.ensure(1));
+  HIPCHK(c, m.ensure(c->mem, 1));  // (an early return leaves it to the ledger)
   HIPCHK(c, hipMemsetAsync(m.p, 0, 8, c->stream));
   hipLaunchKernelGGL(boundary_selftest_kernel, dim3(4096), dim3(256), 0, c->stream, make_tc(p),
                      mode, h0, n, m.p);
@@ -893,15 +861,6 @@ extern "C" int dsx_selftest_boundary(dsx_ctx_t* c, const dsx_params_t* p, int mo
 // --------------------------------------------------------------------------
 // multi-GPU shards (split-and-align across ranks, make.go:22-163 / 277-327)
 // --------------------------------------------------------------------------
-static void release_kept(dsx_ctx* c) {
-  for (auto& k : c->sh.kept) {
-    k.cnt.release();
-    k.list.release();
-  }
-  c->sh.kept.clear();
-  c->sh.nkept = 0;
-}
-
 // Chunks the shard from the cut `entry` (shard_start: speculative, make.go's
 // worker at span*i; or the true entry cut on a re-walk), builds the seam
 // record in c->d_seam, leaves the shard's cuts in c->out and waits.
@@ -932,7 +891,7 @@ static int shard_run(dsx_ctx* c, uint64_t entry, uint32_t rec_flags, bool rewalk
     cc.halo0 = sh.start > 0 ? sh.halo : 0;
     int rc = DSX_OK;
     if (stitch_only) {
-      HIPCHK(c, c->zero_word.ensure(1));
+      HIPCHK(c, c->zero_word.ensure(c->mem, 1));
       HIPCHK(c, hipMemsetAsync(c->zero_word.p, 0, 4, c->stream));
       hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, c->stream, (DevState*)c->state.p,
                          entry);

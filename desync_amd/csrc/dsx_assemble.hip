@@ -377,7 +377,7 @@ extern "C" int dsx_assemble_inplace(dsx_ctx_t* c, const dsx_plan_seg_t* segs, ui
     }
     if (t.asm_stash.n < plan.totals.stash_peak || !t.asm_stash.p) {
       HIPCHK(c, hipStreamSynchronize(st));  // (work in flight may still read the old one)
-      HIPCHK(c, t.asm_stash.ensure(plan.totals.stash_peak));
+      HIPCHK(c, t.asm_stash.ensure(c->mem, plan.totals.stash_peak));
     }
     std::vector<AsmSeg> dev(plan.segs.size());
     for (size_t i = 0; i < dev.size(); ++i) {

@@ -741,17 +741,6 @@ uint64_t many_default_big_blob(const dsx_params_t* p) {
   return std::min<uint64_t>(kManyMaxBatched, (uint64_t)(kWalkLdsCap / 2 - 8) * p->discriminator);
 }
 
-void many_release(dsx_ctx* c) {
-  c->many.ends.release(); c->many.stage.release(); c->many.first.release();
-  c->many.res.release(); c->many.cnt.release(); c->many.runs.release();
-}
-
-uint64_t many_device_bytes(const dsx_ctx* c) {
-  const auto& m = c->many;
-  return (m.ends.n + m.stage.n + m.first.n + m.res.n) * sizeof(uint64_t) +
-         m.cnt.n * sizeof(uint32_t) + m.runs.n * sizeof(ManyRunDev);
-}
-
 // Blob i = [B0, B1) on the one-blob path (run_device, with the dense retry of
 // dsx_cut_device), its cuts into its slots of the staging list.
 static int many_single(dsx_ctx* c, const uint8_t* d_blob, const ManyBlobs& mb,

@@ -14,6 +14,7 @@
 
 #include "../../include/dsx.h"
 #include "dsx_common.h"
+#include "dsx_devmem.h"
 #include "dsx_digest.h"
 #include "dsx_index_plan.h"
 #include "dsx_many.h"
@@ -72,26 +73,10 @@ constexpr uint32_t kQueueDepth = 8;              // DSX_NO_SYNC calls queued per
 constexpr uint32_t kWalkLdsCap = 8192;           // candidates per walk workgroup (2 workgroups per CU)
 constexpr uint64_t kDensePiece = 32ull << 20;    // dense path piece size
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t ensure(size_t want) {
-    if (want <= n && p) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    size_t sz = want < 16 ? 16 : want;
-    hipError_t e = hipMalloc((void**)&p, sz * sizeof(T));
-    if (e == hipSuccess) n = sz;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
+// What a context's ledger (dsx_ctx::mem, dsx_devmem.h) allocates with: the
+// library's only hipMalloc and hipFree.  Its error codes are hipError_t's as int.
+inline int hbm_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+inline int hbm_free(void* p) { return (int)hipFree(p); }
 
 }  // namespace dsx_host
 using namespace dsx_host;
@@ -110,6 +95,10 @@ struct KeptPiece {
 };
 
 struct dsx_ctx {
+  // every byte of HBM the context holds: each DevBuf below, in the scratch
+  // structs and in its live stores and ID sets allocates from it
+  // (stats.device_bytes is its total; dsx_ctx_destroy frees what is left)
+  DevMem mem{hbm_alloc, hbm_free};
   int device = 0;
   int ncu = 256;
   hipStream_t stream = nullptr, copy_stream = nullptr;
@@ -360,7 +349,7 @@ inline hipError_t grow(dsx_ctx* c, DevBuf<T>& b, size_t n, bool headroom = true)
     (void)hipStreamSynchronize(c->copy_stream);
     if (c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
   }
-  return b.ensure(headroom ? n + n / 4 + 64 : n);
+  return (hipError_t)b.ensure(c->mem, headroom ? n + n / 4 + 64 : n);
 }
 
 // The stream a piece's scan waits on for its input bytes (an H2D copy event,
@@ -371,9 +360,10 @@ inline hipError_t scan_wait(dsx_ctx* c, hipEvent_t ev) {
 
 int set_hip_err(dsx_ctx* c, hipError_t e, const char* what);
 
+// (expr: a hipError_t, or a DevBuf::ensure's, which is one as int)
 #define HIPCHK(ctx, expr)                                  \
   do {                                                     \
-    hipError_t e_ = (expr);                                \
+    const hipError_t e_ = static_cast<hipError_t>(expr);   \
     if (e_ != hipSuccess) return set_hip_err(ctx, e_, #expr); \
   } while (0)
 
@@ -423,8 +413,6 @@ int run_many(dsx_ctx* c, const uint8_t* d_blob, uint64_t len, const uint64_t* bl
              uint64_t* n_out, uint64_t* blob_first, uint64_t big_blob, uint64_t group_bytes,
              dsx_many_totals_t* totals, bool dev_out);
 uint64_t many_default_big_blob(const dsx_params_t* p);
-void many_release(dsx_ctx* c);
-uint64_t many_device_bytes(const dsx_ctx* c);
 // host threads (dsx_stream.cpp): fn(0) on the caller, fn(1..parts-1) on a
 // persistent pool; returns when all have returned
 void host_parallel(int parts, const std::function<void(int)>& fn);
@@ -464,5 +452,6 @@ int launch_stitch(dsx_ctx* c, const CallCfg& cc, const PieceCands& pc, uint64_t 
 int launch_digest(dsx_ctx* c, DigestArgs da, uint64_t max_n, int algo, hipStream_t stream = nullptr,
                   uint32_t* queue = nullptr, bool serial = false, uint32_t max_blocks = 0, int pc = -1,
                   uint64_t work = 0);
-void index_release(dsx_ctx* c);   // dsx_index.cpp: frees the pipeline's buffers
-void stream_release(dsx_ctx* c);  // dsx_stream.cpp: frees the stream's buffers
+// what a context holds besides its ledger's memory (dsx_ctx_destroy)
+void index_release(dsx_ctx* c);   // dsx_index.cpp: the pipeline's pinned slots, streams and events
+void stream_release(dsx_ctx* c);  // dsx_stream.cpp: the stream's pinned buffers, stream and events

@@ -59,5 +59,4 @@ int assemble_launch(dsx_ctx* c, const dsx::AsmSeg* d_segs, uint64_t nsegs, void*
 
 constexpr int kIdsetCounters = 4;  // unique, in_seed, size - start, size_not_in_seed
 
-uint64_t idset_device_bytes(const dsx_ctx* c);  // scratch + live sets
-void idset_release(dsx_ctx* c);                 // frees both (dsx_ctx_destroy)
+void idset_release(dsx_ctx* c);  // frees the live sets (dsx_ctx_destroy)

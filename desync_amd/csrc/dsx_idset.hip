@@ -173,18 +173,8 @@ void free_set(dsx_idset* s) {
 
 }  // namespace
 
-uint64_t idset_device_bytes(const dsx_ctx* c) {
-  const IdsetScratch& t = c->idset;
-  uint64_t b = t.slots.n * 4 + t.ids.n + t.ends.n * 8 + t.first_pos.n * 4 + t.seed_pos.n * 4 +
-               t.tot.n * 8 + t.is_null.n + t.asm_segs.n * 8 + t.asm_store.n + t.asm_stash.n;
-  for (const dsx_idset* s : t.live) b += s->ids.n + s->slots.n * 4 + s->sclass.n * 4;
-  return b;
-}
-
 void idset_release(dsx_ctx* c) {
   IdsetScratch& t = c->idset;
-  t.slots.release(), t.ids.release(), t.ends.release(), t.first_pos.release(), t.seed_pos.release();
-  t.tot.release(), t.is_null.release(), t.asm_segs.release(), t.asm_store.release(), t.asm_stash.release();
   for (dsx_idset* s : t.live) free_set(s);
   t.live.clear();
 }
@@ -205,9 +195,9 @@ extern "C" int dsx_idset_create(dsx_ctx_t* c, const void* ids, uint64_t n, uint3
   s->salt = idset_next_salt();
   int rc = DSX_OK;
   auto build = [&]() -> int {
-    HIPCHK(c, s->ids.ensure(n * 32));
-    HIPCHK(c, s->slots.ensure(s->cap));
-    HIPCHK(c, t.tot.ensure(kIdsetCounters));
+    HIPCHK(c, s->ids.ensure(c->mem, n * 32));
+    HIPCHK(c, s->slots.ensure(c->mem, s->cap));
+    HIPCHK(c, t.tot.ensure(c->mem, kIdsetCounters));
     const hipMemcpyKind kind = (flags & known) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (n) HIPCHK(c, hipMemcpyAsync(s->ids.p, ids, n * 32, kind, c->stream));
     const int r = idset_enqueue_build(c, s->ids.p, n, s->slots.p, s->cap, s->salt, t.tot.p);
@@ -404,7 +394,7 @@ extern "C" int dsx_seed_plan(dsx_ctx_t* c, const void* ids, const uint64_t* ends
     for (uint32_t k = 0; k < nseeds; ++k) {
       dsx_idset* s = seeds[k];
       if (!s->n || s->h_sclass.size() == s->n) continue;
-      HIPCHK(c, s->sclass.ensure(s->n));
+      HIPCHK(c, s->sclass.ensure(c->mem, s->n));
       if ((rc = classes(s->ids.p, s->n, s, s->sclass.p, nullptr))) return rc;
       std::vector<uint32_t> h(s->n);
       HIPCHK(c, hipMemcpyAsync(h.data(), s->sclass.p, s->n * 4, hipMemcpyDeviceToHost, st));

@@ -178,7 +178,7 @@ int index_setup(dsx_ctx* c, uint64_t slot_bytes) {
   for (auto& s : c->idx_side)
     if (!s) HIPCHK(c, side_stream_create(&s));
   c->idx_dg_stream = c->idx_side[0];
-  HIPCHK(c, c->idx_side_q.ensure(32 * (dsx_ctx::kIdxSide + 1)));  // (+ the end digest's)
+  HIPCHK(c, c->idx_side_q.ensure(c->mem, 32 * (dsx_ctx::kIdxSide + 1)));  // (+ the end digest's)
   return DSX_OK;
 }
 
@@ -1072,7 +1072,6 @@ void index_release(dsx_ctx* c) {
   c->idx_dg_stream = nullptr;  // (idx_side[0])
   for (auto& s : c->idx_side)
     if (s) (void)hipStreamSynchronize(s), (void)hipStreamDestroy(s), s = nullptr;
-  c->idx_side_q.release();
   for (auto& e : c->idx_stitch_ev)
     if (e) (void)hipEventDestroy(e), e = nullptr;
   for (auto& s : c->idx_slots) {
@@ -1080,9 +1079,6 @@ void index_release(dsx_ctx* c) {
     s = nullptr;
   }
   c->idx_slot_bytes = 0;
-  c->idx_win[0].release();
-  c->idx_win[1].release();
-  c->idx_snap.release();
   for (auto& e : c->idx_copy_ev)
     if (e) (void)hipEventDestroy(e), e = nullptr;
   for (auto& e : c->idx_win_ev)

@@ -26,6 +26,3 @@ struct KnownScratch {
 // bytes, pairs that differed, chunks that hit a bound and were hashed (the
 // resolve's scan); entries the sketch could not insert
 constexpr int kKnownCounters = 8;
-
-uint64_t known_device_bytes(const dsx_ctx* c);
-void known_release(dsx_ctx* c);

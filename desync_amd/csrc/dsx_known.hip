@@ -310,22 +310,6 @@ __global__ __launch_bounds__(kKnownThreads) void known_find_kernel(KnownArgs a) 
 
 using namespace dsx;
 
-uint64_t known_device_bytes(const dsx_ctx* c) {
-  const KnownScratch& w = c->known;
-  uint64_t b = 0;
-  auto add = [&](const auto& d) { b += d.n * sizeof(*d.p); };
-  add(w.tab_fp), add(w.tab_ent), add(w.cand), add(w.flag), add(w.cnt), add(w.take);
-  add(w.beg), add(w.blk), add(w.rblk), add(w.off), add(w.tot);
-  return b;
-}
-
-void known_release(dsx_ctx* c) {
-  KnownScratch& w = c->known;
-  w.tab_fp.release(), w.tab_ent.release(), w.cand.release(), w.flag.release(), w.cnt.release();
-  w.take.release(), w.beg.release(), w.blk.release(), w.rblk.release(), w.off.release();
-  w.tot.release();
-}
-
 extern "C" int dsx_chunk_ids_known(dsx_ctx_t* c, const dsx_store_t* s, const void* d_blob,
                                    uint64_t len, uint64_t start, const uint64_t* ends, uint64_t n,
                                    int algo, void* ids, uint64_t* known_off,

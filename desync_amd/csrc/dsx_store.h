@@ -74,5 +74,4 @@ struct StoreScratch {
 // copy: copied, copied_bytes, present, missing, first_missing; others: [0] a count
 constexpr int kStoreCounters = 6;
 
-uint64_t store_device_bytes(const dsx_ctx* c);  // scratch + live stores
-void store_release(dsx_ctx* c);                 // frees both (dsx_ctx_destroy)
+void store_release(dsx_ctx* c);  // frees the live stores (dsx_ctx_destroy)

@@ -385,23 +385,8 @@ int select_scan_wait(dsx_ctx* c, uint64_t items, Select&& select, u64 (&tot)[kSt
 
 }  // namespace
 
-uint64_t store_device_bytes(const dsx_ctx* c) {
-  const StoreScratch& t = c->store;
-  uint64_t b = t.flag.n + t.blk.n * 8 + t.tot.n * 8 + t.segs.n * 8 + t.offs.n * 8 + t.sizes.n * 8 +
-               t.idx.n * 4 + t.vids.n + t.pids.n + t.pends.n * 8 + t.bounce.n + t.srce.n * 4 +
-               (t.rd_ranges.n + t.rd_pref.n + t.rd_blk.n + t.rd_tot.n + t.rd_segs.n) * 8 +
-               t.rd_first.n * 4;
-  for (const dsx_store* s : t.live) b += s->ids.n + s->ends.n * 8 + s->slots.n * 4 + s->arena.n;
-  return b;
-}
-
 void store_release(dsx_ctx* c) {
   StoreScratch& t = c->store;
-  t.flag.release(), t.blk.release(), t.tot.release(), t.segs.release(), t.offs.release();
-  t.sizes.release(), t.idx.release(), t.vids.release();
-  t.pids.release(), t.pends.release(), t.bounce.release(), t.srce.release();
-  t.rd_ranges.release(), t.rd_pref.release(), t.rd_blk.release(), t.rd_tot.release();
-  t.rd_segs.release(), t.rd_first.release();
   for (dsx_store* s : t.live) free_store(s);
   t.live.clear();
 }
@@ -420,10 +405,10 @@ extern "C" int dsx_store_create(dsx_ctx_t* c, uint64_t arena_bytes, uint64_t max
   s->cap = idset_table_cap(max_chunks);
   s->salt = idset_next_salt();
   auto build = [&]() -> int {
-    HIPCHK(c, s->ids.ensure(max_chunks * 32));
-    HIPCHK(c, s->ends.ensure(max_chunks));
-    HIPCHK(c, s->slots.ensure(s->cap));
-    HIPCHK(c, s->arena.ensure(arena_bytes));
+    HIPCHK(c, s->ids.ensure(c->mem, max_chunks * 32));
+    HIPCHK(c, s->ends.ensure(c->mem, max_chunks));
+    HIPCHK(c, s->slots.ensure(c->mem, s->cap));
+    HIPCHK(c, s->arena.ensure(c->mem, arena_bytes));
     HIPCHK(c, hipMemsetAsync(s->slots.p, 0xFF, s->cap * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSX_OK;

@@ -329,21 +329,16 @@ void stream_release(dsx_ctx* c) {
   if (s.h) (void)hipHostFree(s.h);
   s.h = nullptr;
   for (int i = 0; i < kSlots; ++i) {
-    s.dbuf[i].release();
-    s.dout[i].release();
     if (s.hcut[i]) (void)hipHostFree(s.hcut[i]);
     s.hcut[i] = nullptr;
     if (s.copy_ev[i]) (void)hipEventDestroy(s.copy_ev[i]);
     if (s.done_ev[i]) (void)hipEventDestroy(s.done_ev[i]);
     if (s.stitch_ev[i]) (void)hipEventDestroy(s.stitch_ev[i]);
     s.copy_ev[i] = s.done_ev[i] = s.stitch_ev[i] = nullptr;
-    s.dids[i].release();
     if (s.hids[i]) (void)hipHostFree(s.hids[i]);
     s.hids[i] = nullptr;
     s.hids_cap[i] = 0;
   }
-  s.rng.release();
-  s.dq.release();
   if (s.dg_stream) (void)hipStreamDestroy(s.dg_stream);
   s.dg_stream = nullptr;
   if (s.hstate) (void)hipHostFree(s.hstate);

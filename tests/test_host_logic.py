@@ -596,6 +596,27 @@ def test_index_plan_model(tmp_path):
     assert r.stdout.splitlines()[-1].startswith("index plan model ok: "), r.stdout[-1000:]
 
 
+def test_devmem_model(tmp_path):
+    """dsx_devmem.h alone, under the host sanitizers: the ledger and DevBuf over
+    a recording fake allocator, seeded scripts of ensure, growth, release,
+    copied handles, failed allocations and release_all; a broken invariant is
+    a non-zero exit (tests/devmem_model.cpp)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    assert cxx, "no host C++ compiler"
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "devmem_model")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined",
+           "-fno-sanitize-recover=undefined", "-I" + os.path.join(repo, "desync_amd", "csrc"),
+           os.path.join(repo, "tests", "devmem_model.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert r.stdout.splitlines()[-1].startswith("devmem model ok: "), r.stdout[-1000:]
+
+
 # --------------------------------------------- run_ids's schedule (no GPU)
 _KiB, _GiB = 1 << 10, 1 << 30
 
