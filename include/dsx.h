@@ -134,7 +134,12 @@ int dsx_progress(dsx_ctx_t *ctx, uint64_t *bytes);
  * needs the general path (dense candidates, a stitch repair) is re-run from
  * the blob inside dsx_result().  If cap is too small the call returns
  * DSX_E_CAPACITY and *n_out holds the required count (an upper bound of
- * len/min + 2 always suffices).  A queued call's stitch publishes its state
+ * len/min + 2 always suffices; cap == 0 with out_ends == NULL is the counting
+ * call).  A failing call writes nothing at or behind out_ends[cap]; a host
+ * out_ends is not written at all, what a device out_ends holds below cap is
+ * unspecified (a call of several pieces has written the pieces that fitted).
+ * The context's next call is not affected.  A queued call's DSX_E_CAPACITY and
+ * count come from its dsx_result().  A queued call's stitch publishes its state
  * into pinned host memory and dsx_result() polls it (no event per call).
  * (The diagnostic build libdsx_diag.so also has DSX_FUSE=1: the stitch of a
  * queued one-piece call as tasks inside the next queued calls' scans; the
@@ -322,6 +327,12 @@ int dsx_host_sha512_256(const uint8_t *const *ptrs, const uint64_t *lens, uint64
  *   rank's resolve returns DSX_E_PEER instead of waiting for a record that
  *   never comes.  d_shard passed to dsx_shard_local must stay valid until
  *   dsx_shard_resolve returns DSX_OK.
+ *   If cap is too small for this rank's list, resolve returns DSX_E_CAPACITY
+ *   with the required count in *n_out (shard_len/min + 4 + DSX_SEAM_MAX_CUTS
+ *   always suffices) and writes nothing to out_ends, host or device; the
+ *   other ranks' results are not affected, and the rank may call resolve
+ *   again with a larger cap over the same records.  With DSX_E_RESYNC and
+ *   DSX_E_PEER *n_out is 0 and out_ends is not written.
  * Seam records are plain bytes. */
 #define DSX_SEAM_MAX_CANDS 1024
 #define DSX_SEAM_MAX_CUTS 1024
@@ -370,8 +381,11 @@ int dsx_shard_resolve(dsx_ctx_t *ctx, const dsx_seam_t *all, int nranks, int ran
  *     and rewritten my_seam, device memory), DSX_E_PEER, or an error (then
  *     my_seam is marked DSX_SEAM_ERROR when the failure happened after the
  *     agreement: exchange once more so the peers learn of it).  With an
- *     agreed code of 2 it returns this rank's own failure (DSX_E_CAPACITY) or
- *     DSX_E_PEER. */
+ *     agreed code of 2 it returns this rank's own failure (DSX_E_CAPACITY,
+ *     with the required count in *n_out and nothing written to out_ends) or
+ *     DSX_E_PEER (*n_out is 0; a list that fitted has been written).  After
+ *     either, the ranks may resolve again over the same records.
+ *   dsx_shard_resolve_async needs a non-NULL out_ends even with cap == 0. */
 int dsx_shard_resolve_async(dsx_ctx_t *ctx, const dsx_seam_t *all, int nranks, int rank,
                             uint64_t *out_ends, uint64_t cap, int32_t *d_code);
 int dsx_shard_collect(dsx_ctx_t *ctx, dsx_seam_t *my_seam, const int32_t *d_agreed,

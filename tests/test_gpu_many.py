@@ -219,12 +219,13 @@ def test_capacity_and_reuse(dctx):
     assert np.array_equal(desync_amd.cut_device(t.data_ptr(), n_bytes, *SMALL, ctx=dctx), one)
     # cap = needed - 1
     p = desync_amd.Params(*SMALL)
-    out = np.zeros(wends.size, dtype=np.uint64)
+    out = np.full(wends.size, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
     n = ctypes.c_uint64()
     rc = _lib.lib().dsx_cut_device_many(dctx.h, ctypes.c_void_p(t.data_ptr()), n_bytes,
                                         be.ctypes.data, be.size, ctypes.byref(p.c), out.ctypes.data,
                                         wends.size - 1, ctypes.byref(n), None, None, None, 0)
     assert rc == _lib.DSX_E_CAPACITY and n.value == wends.size
+    assert np.all(out == np.uint64(0xA5A5A5A5A5A5A5A5))  # a failing call leaves the host buffer alone
     check_lists(many(dctx, t, be, SMALL), (wends, wfirst), be)
     assert np.array_equal(desync_amd.cut_device(t.data_ptr(), n_bytes, *SMALL, ctx=dctx), one)
     # one blob equals cut_device; no blob at all is no chunk
