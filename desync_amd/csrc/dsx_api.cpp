@@ -513,14 +513,21 @@ extern "C" int dsx_result(dsx_ctx_t* c, uint64_t* n_out) {
 extern "C" int dsx_cut_device(dsx_ctx_t* c, const void* d_blob, uint64_t len, const dsx_params_t* p,
                               uint64_t* out_ends, uint64_t cap, uint64_t* n_out, uint32_t flags) {
   if (!c || !p || !n_out || (len && !d_blob) || (cap && !out_ends)) return DSX_E_INVAL;
-  c->cancel.store(0);
-  int rc = ensure_attr_walk(c);
-  if (rc) return rc;
-  *n_out = 0;
-  if (len == 0) return DSX_OK;  // TestChunkerEmptyFile: no chunks
   const bool dev_out = (flags & DSX_OUT_DEVICE) != 0;
-  const uint64_t need = len / p->min + 2;
   const bool queued = (flags & DSX_NO_SYNC) && dev_out;
+  *n_out = 0;
+  if (queued && len && c->pend.size() >= kQueueDepth) {
+    c->err = "too many queued DSX_NO_SYNC calls (collect them with dsx_result)";
+    return DSX_E_STATE;
+  }
+  // (an empty blob too: what a chain call is allowed depends on its kind alone)
+  int rc = chain_begin(c, queued ? ChainKind::kCutQueued : ChainKind::kCut);
+  if (rc) return rc;
+  c->cancel.store(0);
+  rc = ensure_attr_walk(c);
+  if (rc) return rc;
+  if (len == 0) return DSX_OK;  // TestChunkerEmptyFile: no chunks
+  const uint64_t need = len / p->min + 2;
   const bool fuse = queued && behind_ok(c, d_blob, len, p);
   if (!fuse) {  // every other call starts after the stitches still behind
     rc = flush_tasks(c);
@@ -531,10 +538,6 @@ extern "C" int dsx_cut_device(dsx_ctx_t* c, const void* d_blob, uint64_t len, co
     if (rc) return rc;
   }
   if (queued) {
-    if (c->pend.size() >= kQueueDepth) {
-      c->err = "too many queued DSX_NO_SYNC calls (collect them with dsx_result)";
-      return DSX_E_STATE;
-    }
     CallCfg cc{p, len, 0, kRound, out_ends, cap, false};
     cc.behind = fuse;
     dsx_ctx::Pending q;
@@ -631,11 +634,13 @@ extern "C" int dsx_cut_device_many(dsx_ctx_t* c, const void* d_blob, uint64_t le
   if (nblobs && blob_ends[nblobs - 1] != len) return refuse("cut_device_many: the last blob does not end the buffer");
   if (p->min < (uint64_t)kRound || p->discriminator == 0) return refuse("cut_device_many: parameters not from dsx_params_init");
 
+  int rc = chain_begin(c, ChainKind::kMany);
+  if (rc) return rc;
   c->cancel.store(0);
   *n_out = 0;
   if (totals) *totals = dsx_many_totals_t{};
   if (nblobs == 0) return DSX_OK;
-  int rc = ensure_attr_walk(c);
+  rc = ensure_attr_walk(c);
   if (rc) return rc;
   // queued calls: as a synchronous dsx_cut_device treats them
   rc = flush_tasks(c);
@@ -975,8 +980,12 @@ extern "C" int dsx_shard_local(dsx_ctx_t* c, const void* d_shard, uint64_t halo,
     return DSX_E_INVAL;
   const bool async = (flags & DSX_NO_SYNC) != 0;
   if (shard_start > 0 && halo < kRound) return DSX_E_INVAL;
+  // (the shard of an earlier dsx_shard_local is gone from here on; this
+  // call's own run below, and shard_outcome's re-walk and redo, own the new one)
+  int rc = chain_begin(c, ChainKind::kShardLocal);
+  if (rc) return rc;
   c->cancel.store(0);
-  int rc = ensure_attr_walk(c);
+  rc = ensure_attr_walk(c);
   if (rc) return rc;
   auto& sh = c->sh;
   sh.d = (const uint8_t*)d_shard;
@@ -986,7 +995,6 @@ extern "C" int dsx_shard_local(dsx_ctx_t* c, const void* d_shard, uint64_t halo,
   sh.total = total;
   sh.p = *p;
   sh.nspec = 0;
-  sh.valid = false;
   if (shard_len == 0) {
     dsx_seam_t z;
     memset(&z, 0, sizeof z);
@@ -1002,12 +1010,12 @@ extern "C" int dsx_shard_local(dsx_ctx_t* c, const void* d_shard, uint64_t halo,
     hipLaunchKernelGGL(state_init_kernel, dim3(1), dim3(64), 0, c->stream, (DevState*)c->state.p,
                        shard_start);
     HIPCHK(c, hipGetLastError());
-    sh.valid = true;
+    c->owner.shard_ready();
     return seam_out(c, seam, (flags & DSX_SEAM_DEVICE) != 0);
   }
   rc = shard_run(c, shard_start, 0u, false, async);
   if (rc) return rc;
-  sh.valid = true;
+  c->owner.shard_ready();
   return seam_out(c, seam, (flags & DSX_SEAM_DEVICE) != 0, !async);
 }
 
@@ -1071,7 +1079,9 @@ extern "C" int dsx_shard_resolve(dsx_ctx_t* c, const dsx_seam_t* all, int nranks
       (cap && !out_ends) || (flags & ~(DSX_SEAM_DEVICE | DSX_OUT_DEVICE)) != 0)
     return DSX_E_INVAL;
   auto& sh = c->sh;
-  if (!sh.valid) return DSX_E_STATE;
+  // a chain call since dsx_shard_local left another call's cuts in c->out and
+  // c->state: a stale shard never resolves to a list
+  if (int rc = c->owner.resolve(&c->err)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const bool seam_dev = (flags & DSX_SEAM_DEVICE) != 0, out_dev = (flags & DSX_OUT_DEVICE) != 0;
   const dsx_seam_t* d_all = all;
@@ -1116,7 +1126,9 @@ extern "C" int dsx_shard_resolve_async(dsx_ctx_t* c, const dsx_seam_t* all, int 
   if (!c || !all || nranks < 1 || rank < 0 || rank >= nranks || !out_ends || !d_code)
     return DSX_E_INVAL;
   auto& sh = c->sh;
-  if (!sh.valid) return DSX_E_STATE;
+  // a chain call since dsx_shard_local left another call's cuts in c->out and
+  // c->state: a stale shard never resolves to a list
+  if (int rc = c->owner.resolve(&c->err)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, grow(c, c->d_ext, DSX_SEAM_MAX_CUTS + 4));
   HIPCHK(c, grow(c, c->d_info, 8));
@@ -1133,7 +1145,7 @@ extern "C" int dsx_shard_resolve_async(dsx_ctx_t* c, const dsx_seam_t* all, int 
   HIPCHK(c, hipGetLastError());
   sh.pend_rank = rank;
   sh.pend_cap = cap;
-  sh.pending = true;
+  c->owner.resolve_launched();
   return DSX_OK;
 }
 
@@ -1142,8 +1154,12 @@ extern "C" int dsx_shard_collect(dsx_ctx_t* c, dsx_seam_t* my_seam, const int32_
   DSX_FLUSH_BEHIND(c);
   if (!c || !my_seam || !n_out || (d_agreed && !agreed)) return DSX_E_INVAL;
   auto& sh = c->sh;
-  if (!sh.pending) return DSX_E_STATE;
-  sh.pending = false;
+  if (int rc = c->owner.collect(&c->err)) {
+    // (a stale shard's emit may still be writing the caller's list)
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+  }
   HIPCHK(c, hipSetDevice(c->device));
   int32_t* h_code = (int32_t*)(c->h_res + 3);
   if (d_agreed)

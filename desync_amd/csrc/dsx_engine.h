@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dsx.h"
+#include "dsx_chain_owner.h"
 #include "dsx_common.h"
 #include "dsx_devmem.h"
 #include "dsx_digest.h"
@@ -244,10 +245,8 @@ struct dsx_ctx {
     uint64_t halo = 0, start = 0, len = 0, total = 0;
     dsx_params_t p{};
     uint64_t nspec = 0;  // speculative cuts in ctx->out (~0: unknown, asynchronous local)
-    bool pending = false;              // dsx_shard_resolve_async awaits dsx_shard_collect
-    int pend_rank = 0;
+    int pend_rank = 0;                 // dsx_shard_resolve_async's, for dsx_shard_collect
     uint64_t pend_cap = 0;
-    bool valid = false;
     bool dense = false;                // scanned on the dense path (lists not kept)
     // the shard's pieces' region lists: kept[0 .. nkept) of this run; the
     // buffers stay allocated across runs (a hipFree per step would wait for
@@ -259,6 +258,10 @@ struct dsx_ctx {
   DevBuf<uint32_t> zero_word;  // an overflow flag that stays 0 (stitch-only re-runs)
   DevBuf<uint64_t> d_ext, d_info, d_emit;
   uint64_t* h_res = nullptr;  // pinned: shard_emit_kernel status / count / entry
+  // who owns `state` and `out` between calls: whether the shard is valid,
+  // stale or awaits its collect, and which chain calls a live stream or
+  // queue refuses (dsx_chain_owner.h; chain_begin() below)
+  ChainOwner owner;
 
   dsx_stats_t stats{};
   // in-kernel stamps of the scan launches (dsx_stamps_begin .. dsx_stamps_end):
@@ -350,6 +353,16 @@ inline hipError_t grow(dsx_ctx* c, DevBuf<T>& b, size_t n, bool headroom = true)
     if (c->scan_stream != c->stream) (void)hipStreamSynchronize(c->scan_stream);
   }
   return (hipError_t)b.ensure(c->mem, headroom ? n + n / 4 + 64 : n);
+}
+
+// A chain call of kind k is about to start: every entry point that runs a
+// chunking chain asks here after its argument refusals and before its first
+// launch or allocation.  DSX_E_STATE (c->err names the protocol): refused,
+// nothing changed.
+inline int chain_begin(dsx_ctx* c, ChainKind k) {
+  const auto& s = c->st;
+  const ChainView v{s.active && !(s.done && s.cuts.empty()), (uint32_t)c->pend.size()};
+  return c->owner.begin(k, v, &c->err);
 }
 
 // The stream a piece's scan waits on for its input bytes (an H2D copy event,

@@ -1100,6 +1100,7 @@ extern "C" int dsx_index_fd(dsx_ctx_t* c, int fd, uint64_t off, uint64_t len, co
     if (end < 0) return DSX_E_IO;
     len = (uint64_t)end > off ? (uint64_t)end - off : 0;
   }
+  if (const int rc = chain_begin(c, ChainKind::kIndexFd)) return rc;
   FdSrc s{fd, off};
   const int rc = run_index(c, p, algo, len, fill_fd, &s, out_ends, ids, cap, n_out);
   c->cancel.store(0);  // a dsx_cancel() issued before or during this call ends here
@@ -1117,6 +1118,7 @@ extern "C" int dsx_cut_fd(dsx_ctx_t* c, int fd, uint64_t off, uint64_t len, cons
     if (end < 0) return DSX_E_IO;
     len = (uint64_t)end > off ? (uint64_t)end - off : 0;
   }
+  if (const int rc = chain_begin(c, ChainKind::kCutFd)) return rc;
   FdSrc s{fd, off};
   const int rc = run_index(c, p, -1, len, fill_fd, &s, out_ends, nullptr, cap, n_out);
   c->cancel.store(0);
@@ -1127,6 +1129,7 @@ extern "C" int dsx_cut_host(dsx_ctx_t* c, const void* h_blob, uint64_t len, cons
                             uint64_t* out_ends, uint64_t cap, uint64_t* n_out) {
   DSX_FLUSH_BEHIND(c);
   if (!c || !p || !n_out || (len && !h_blob) || (cap && !out_ends)) return DSX_E_INVAL;
+  if (const int rc = chain_begin(c, ChainKind::kCutHost)) return rc;
   MemSrc s{(const uint8_t*)h_blob};
   const int rc = run_index(c, p, -1, len, fill_mem, &s, out_ends, nullptr, cap, n_out);
   c->cancel.store(0);
@@ -1139,6 +1142,7 @@ extern "C" int dsx_index_host(dsx_ctx_t* c, const void* h_blob, uint64_t len, co
   DSX_FLUSH_BEHIND(c);
   if (!c || !p || !n_out || (len && !h_blob) || (cap && (!out_ends || !ids)) || bad_algo(algo))
     return DSX_E_INVAL;
+  if (const int rc = chain_begin(c, ChainKind::kIndexHost)) return rc;
   MemSrc s{(const uint8_t*)h_blob};
   const int rc = run_index(c, p, algo, len, fill_mem, &s, out_ends, ids, cap, n_out, s.p);
   c->cancel.store(0);

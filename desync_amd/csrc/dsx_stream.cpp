@@ -104,6 +104,9 @@ int st_collect(dsx_ctx* c);
 int st_issue(dsx_ctx* c, uint64_t len, bool last) {
   auto& s = c->st;
   if ((int)s.fly.size() >= kSlots) return st_collect(c);  // st_pump comes back (its sched may move)
+  // (never refused: the stream owns the chain.  A finished stream that
+  // dsx_stream_advance or dsx_stream_flush starts again stales a shard here.)
+  if (const int rc = chain_begin(c, ChainKind::kStreamBatch)) return rc;
   const int slot = s.next_slot;
   s.next_slot = (slot + 1) % kSlots;
   const uint64_t P = s.sched;
@@ -351,11 +354,9 @@ extern "C" int dsx_stream_begin(dsx_ctx_t* c, const dsx_params_t* p) {
   auto& s = c->st;
   // one stream per context (its scratch and carried state live here): a
   // second Chunker on a context whose stream is still being read is refused
-  // instead of silently resetting the first one
-  if (s.active && !(s.done && s.cuts.empty())) {
-    c->err = "a stream is already active on this context (dsx_stream_end it first)";
-    return DSX_E_STATE;
-  }
+  // instead of silently resetting the first one, and so is a stream begun
+  // while queued calls wait for their dsx_result (dsx_chain_owner.h)
+  if (const int rc = chain_begin(c, ChainKind::kStreamBegin)) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   int rc = ensure_attr_walk(c);
   if (!rc) rc = st_setup(c);

@@ -101,10 +101,39 @@ int dsx_abi_version(void);
 /* ---- context ---------------------------------------------------------------- */
 typedef struct dsx_ctx dsx_ctx_t;
 
-/* Owns HIP streams, device scratch and pinned staging on `device`. */
+/* Owns HIP streams, device scratch and pinned staging on `device`.
+ *
+ * One chain state per context.  A *chain call* runs a chunking chain on the
+ * context: dsx_cut_device (with DSX_NO_SYNC or without), dsx_cut_device_many,
+ * dsx_cut_host, dsx_cut_fd, dsx_index_host, dsx_index_fd, dsx_stream_begin and
+ * the stream's batches, dsx_shard_local (and the re-walk or redo inside a
+ * resolve).  They all share the context's one chain state and staging list.
+ * Every other call is *neutral*: dsx_chunk_ids, dsx_ids_*, the ID sets and
+ * dsx_dedup, the seed plans and dsx_assemble*, dsx_store_*, dsx_read_ranges,
+ * dsx_chunk_ids_known, dsx_aead_*, dsx_copy, dsx_sync, dsx_get_stats, the
+ * stamps.  Neutral calls may run anywhere -- inside a stream, between
+ * dsx_shard_local and its resolve, between a queued call and its dsx_result --
+ * and change no result.  For the three protocols that span several calls:
+ *   - queued calls: any call may run between a DSX_NO_SYNC call and its
+ *     dsx_result (dsx_result's synchronous redo is itself a chain call);
+ *   - shards: a chain call between dsx_shard_local and the resolve that
+ *     returns DSX_OK makes the shard stale: dsx_shard_resolve,
+ *     dsx_shard_resolve_async and dsx_shard_collect then return DSX_E_STATE and
+ *     write no list, and the caller starts the round over with
+ *     dsx_shard_local.  A stale shard never resolves to a list;
+ *   - streams: while a stream is unfinished (begun, and not every chunk up to
+ *     the end of its input popped, nor ended) a chain call on its context is
+ *     refused with DSX_E_STATE before any device work, and the stream goes on
+ *     unharmed.  dsx_stream_begin with uncollected queued calls is refused the
+ *     same way: collect them with dsx_result first.
+ * After such a DSX_E_STATE dsx_last_error names the protocol that was
+ * disturbed first ("stream: ...", "queued calls: ...", "shard: ...").  Work
+ * that must overlap a stream or a shard round takes a context of its own.
+ * An argument refusal (DSX_E_INVAL) comes first and disturbs nothing. */
 int dsx_ctx_create(int device, dsx_ctx_t **out);
 int dsx_ctx_destroy(dsx_ctx_t *ctx);
-/* Human-readable detail for the last DSX_E_HIP / DSX_E_INTERNAL on ctx
+/* Human-readable detail for the last DSX_E_HIP / DSX_E_INTERNAL on ctx, and for
+ * a DSX_E_STATE of the chain-state rule above
  * (ctx == NULL: the reason the last dsx_ctx_create failed). */
 const char *dsx_last_error(dsx_ctx_t *ctx);
 /* Request cancellation of the running/next call; it returns DSX_E_INTERRUPTED. */
@@ -218,7 +247,12 @@ int dsx_cut_fd(dsx_ctx_t *ctx, int fd, uint64_t off, uint64_t len, const dsx_par
  * One stream per context (a Chunker owns its context, as each Go Chunker owns
  * its buffer and hash state, chunker.go:108-131).
  * begin:  starts a stream at position 0 with params p (NewChunker).  Returns
- *         DSX_E_STATE while another stream on ctx is unfinished.
+ *         DSX_E_STATE while another stream on ctx is unfinished, or while
+ *         queued DSX_NO_SYNC calls wait for their dsx_result.  Until the
+ *         stream is finished or ended, every other chain call on ctx is
+ *         refused ("One chain state per context", at dsx_ctx_create).
+ *         (dsx_stream_advance and dsx_stream_flush start a finished stream
+ *         again: collect queued calls before them, as before begin.)
  * end:    drops the stream (the context can begin a new one).
  * buffer: room for `want` bytes at the tail of the library's pinned host
  *         buffer; *ptr is where the caller writes them (e.g. the reader
@@ -326,7 +360,11 @@ int dsx_host_sha512_256(const uint8_t *const *ptrs, const uint64_t *lens, uint64
  *   DSX_SEAM_ERROR: the caller all-gathers it once more so that every other
  *   rank's resolve returns DSX_E_PEER instead of waiting for a record that
  *   never comes.  d_shard passed to dsx_shard_local must stay valid until
- *   dsx_shard_resolve returns DSX_OK.
+ *   dsx_shard_resolve returns DSX_OK.  A chain call on ctx between
+ *   dsx_shard_local and that resolve makes the shard stale: resolve (and
+ *   resolve_async, collect) then return DSX_E_STATE and the round starts over
+ *   with dsx_shard_local ("One chain state per context", at dsx_ctx_create).
+ *   A resolved shard can be resolved again until the next chain call.
  *   If cap is too small for this rank's list, resolve returns DSX_E_CAPACITY
  *   with the required count in *n_out (shard_len/min + 4 + DSX_SEAM_MAX_CUTS
  *   always suffices) and writes nothing to out_ends, host or device; the
