@@ -22,6 +22,7 @@ mirror of the reference's Go API for that path:
     NewXChaCha20Poly1305, Converters, Compressor, StoreOptions  (encrypt.go, converter.go, store.go)
     DeviceStore.Seal, PutSealed, WriteLocal, ReadLocal      (encrypt.go, local.go)
     Copy, Cache, NewCache, DeviceStore.CopyFrom, Grow       (copy.go, cache.go)
+    DeviceStore(track=, evict=), Track, Touch, Evict, stamps  (least recently used eviction; no reference counterpart)
     NewIndexReadSeeker, IndexPos, Cat, read_ranges, DeviceIndex  (readseeker.go, cmd/desync/cat.go)
 
 There is no CPU fallback: without libdsx.so or a GPU, calls raise.

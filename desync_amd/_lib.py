@@ -64,7 +64,7 @@ EXPORTS = (
     "dsx_store_resolve", "dsx_store_verify", "dsx_store_prune", "dsx_store_copy",
     "dsx_aead_seal", "dsx_aead_open", "dsx_selftest_poly1305", "dsx_cut_device_many",
     "dsx_inplace_plan", "dsx_assemble_inplace", "dsx_chunk_keep", "dsx_read_ranges", "dsx_read_plan",
-    "dsx_chunk_ids_known",
+    "dsx_chunk_ids_known", "dsx_store_track", "dsx_store_touch", "dsx_store_stamps", "dsx_store_evict",
 )
 DSX_DIGEST_SHA512_256 = 0
 DSX_DIGEST_SHA256 = 1
@@ -81,6 +81,8 @@ DSX_STORE_DEVICE = 128
 DSX_ASSEMBLE_UNALIGNED = 256
 DSX_PRUNE_REMOVE = 512
 DSX_COPY_ALL = 1024
+DSX_EVICT_DRY = 8192       # dsx_store_evict: select and report, change nothing
+DSX_STAMP_NOW = 0          # dsx_store_touch: the store's next clock value
 DSX_INPLACE_ASCENDING = 2048
 DSX_INPLACE_DESCENDING = 4096
 DSX_INPLACE_SAVE = 0       # dsx_inplace_launch_t.kind
@@ -187,6 +189,14 @@ class StoreCopyTotals(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in
                 ("total", "copied", "copied_bytes", "present", "repeats", "missing", "first_missing",
                  "reserved")]
+
+
+class StoreEvictTotals(ctypes.Structure):
+    """dsx_store_evict_totals_t."""
+
+    _fields_ = [(n, ctypes.c_uint64) for n in
+                ("entries", "evicted", "evicted_bytes", "kept", "kept_bytes", "moved", "moved_bytes",
+                 "pinned", "evictable", "evictable_bytes", "cutoff")] + [("reserved", ctypes.c_uint64 * 2)]
 
 
 class Range(ctypes.Structure):
@@ -412,6 +422,10 @@ def lib():
             "dsx_store_verify": (i32, [vp, vp, i32, vp, u64, P(u64)]),
             "dsx_store_prune": (i32, [vp, vp, vp, u64, u64, P(StorePruneTotals), u32]),
             "dsx_store_copy": (i32, [vp, vp, vp, vp, u64, P(StoreCopyTotals), u32]),
+            "dsx_store_track": (i32, [vp, vp]),
+            "dsx_store_touch": (i32, [vp, vp, vp, u64, u64, P(u64), u32]),
+            "dsx_store_stamps": (i32, [vp, vp, u64, u64, vp, P(u64), u32]),
+            "dsx_store_evict": (i32, [vp, vp, u64, u64, vp, u64, vp, u64, u64, P(StoreEvictTotals), u32]),
             "dsx_read_ranges": (i32, [vp, vp, vp, vp, u64, u64, vp, u64, vp, u64, vp, u64,
                                       P(ReadTotals), u32]),
             "dsx_read_plan": (i32, [vp, u64, u64, vp, u64, vp, u64, P(u64)]),

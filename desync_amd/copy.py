@@ -93,7 +93,10 @@ class Cache:
     chunk is looked for in ``l`` first; one fetched from ``s`` is stored in
     ``l`` too.  With two :class:`DeviceStore` s of one context the fetch is a
     dsx_store_copy ``s -> l``, and :func:`desync_amd.AssembleBlob` fills ``l``
-    with one copy of everything its plan needs before it reads ``l`` in place."""
+    with one copy of everything its plan needs before it reads ``l`` in place.
+    A local ``DeviceStore(evict=True)`` makes it a bounded cache: a fetch that
+    does not fit evicts the least recently used chunks of ``l`` first (the
+    reference's cache grows without bound and is cleaned by ``desync prune``)."""
 
     def __init__(self, s, l):  # noqa: E741 (the reference's field names)
         self.s, self.l = s, l

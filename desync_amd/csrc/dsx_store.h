@@ -25,9 +25,11 @@ struct dsx_store {
   DevBuf<uint64_t> ends;   // max_chunks words, cumulative
   DevBuf<uint32_t> slots;  // cap words
   DevBuf<uint8_t> arena;   // arena_bytes
+  DevBuf<uint64_t> stamps; // max_chunks words, once tracked
   uint64_t max_chunks = 0, arena_bytes = 0, cap = 0, salt = 0;
   uint64_t chunks = 0, bytes = 0;
-  bool broken = false;
+  uint64_t clock = 0;
+  bool broken = false, tracked = false;
 };
 
 // What a kernel takes of a store, by value in its arguments: n entries, bytes
@@ -42,6 +44,11 @@ struct StoreView {
   uint64_t n, mask, salt, bytes;
   uint8_t* arena;
 };
+
+// The stamp ++clock hands out.  The clock saturates: at UINT64_MAX (reached
+// only through a caller's own stamp) every later use is stamped UINT64_MAX, so
+// a stamp never wraps to the oldest value; such uses are ordered by entry number.
+inline uint64_t next_stamp(const dsx_store* s) { return s->clock == UINT64_MAX ? UINT64_MAX : s->clock + 1; }
 
 inline StoreView view_of(const dsx_store* s) {
   return StoreView{s->ids.p, s->ends.p, s->slots.p, s->chunks, s->cap - 1, s->salt, s->bytes, s->arena.p};
@@ -61,6 +68,12 @@ struct StoreScratch {
   DevBuf<unsigned long long> pends;   // ... and their new ends (copied over the store's after the arena moved)
   DevBuf<uint8_t> bounce;             // prune: one window of the compacted arena
   DevBuf<uint32_t> srce;              // copy: the source store's entry number per ID
+  DevBuf<unsigned long long> pstamps; // prune, evict of a tracked store: the survivors' stamps, packed
+  // dsx_store_evict: pinned[e], the selection's state (kEvictSel words), one histogram of 256
+  // {entries, bytes} pairs per pass, the boundary class's {entries, bytes} per workgroup,
+  // the evicted IDs packed
+  DevBuf<uint8_t> ev_pinned, ev_ids;
+  DevBuf<unsigned long long> ev_sel, ev_hist, ev_blk;
   // dsx_read_ranges (dsx_read.hip): the staged ranges (3 words each), each range's first chunk,
   // its table slots as a prefix sum inside its workgroup, the workgroups' sums, the counters,
   // and the gather table (AsmSeg records)
@@ -73,5 +86,11 @@ struct StoreScratch {
 // UINT64_MAX - the first removed byte's offset (0: none), -, moved, moved_bytes;
 // copy: copied, copied_bytes, present, missing, first_missing; others: [0] a count
 constexpr int kStoreCounters = 6;
+
+// dsx_store_evict's selection state: the stamp bytes chosen so far (after the
+// last pass: the cutoff stamp T), the needs not yet met by the entries below
+// them, 1 if the unpinned entries cannot meet the needs, then the pin launch's sums
+enum { kSelPrefix = 0, kSelNeedChunks, kSelNeedBytes, kSelFailed, kSelEvictable, kSelEvictableBytes,
+       kSelPinned, kEvictSel };
 
 void store_release(dsx_ctx* c);  // frees the live stores (dsx_ctx_destroy)

@@ -64,6 +64,20 @@
 // claim compares none.  src is only read.  A store grows by a copy of all its
 // entries into a larger one.
 //
+// An evict (dsx_store_evict, of a store that tracks use: one stamp per entry)
+// is a prune whose keep mask the device chooses (Eviction):
+//   pins     the call's own table over the pin list, pinned[e], the sums of the rest;
+//   descent  per stamp byte, from the clock's highest down: a histogram of 256
+//            {entries, bytes} buckets over the unpinned entries under the bytes
+//            chosen so far, then one workgroup picks the bucket in which the
+//            least recently used prefix that makes the room ends
+//            (dsx_evict_geom.h); no host wait between the passes;
+//   class    {entries, bytes} of the cutoff stamp's class per workgroup, scanned;
+//   keep     keep[e] = pinned, or newer than the cutoff, or of its class behind
+//            a class prefix that already meets the needs; what mark leaves;
+//   (the host reads the totals; from here on it is the prune's compact, move
+//   and rebuild, one function for both, with the stamps carried along)
+//
 // Out of scope: compression and encryption converters; persistence
 // (dsx_store_entries plus the arena are enough for a caller to save and reload
 // one); use from a second context or GPU.
@@ -77,6 +91,7 @@
 
 #include "dsx_callargs.h"
 #include "dsx_engine.h"
+#include "dsx_evict_geom.h"
 #include "dsx_idset_dev.h"
 
 namespace dsx {
@@ -267,6 +282,10 @@ struct PruneArgs {
   uint64_t* new_ends;  // [kept]
   AsmSeg* segs;        // [kept]
   u64 n_keep;          // the total the host read: the compaction's ranks stay below it
+  const uint64_t* stamps;  // a tracked store's stamps, else null ...
+  uint64_t* new_stamps;    // ... and [kept], the survivors' (null with stamps)
+  uint8_t* ev_ids;     // an evict that reports its victims: [n_ev] their IDs in entry order, else null
+  u64 n_ev;
 };
 
 // One lane per entry: keep[e] = the entry's ID is among the call's (is not,
@@ -314,9 +333,18 @@ __global__ __launch_bounds__(kStoreThreads) void store_compact_kernel(PruneArgs 
   const u64 rank = a.blk[2 * (u64)blockIdx.x] + before[0];
   const u64 off = a.blk[2 * (u64)blockIdx.x + 1] + before[1];
   const bool moved = keep && off != old;
-  if (keep && rank < a.n_keep)  // (always: the ranks are the scan of the flags the total counted)
+  if (keep && rank < a.n_keep) {  // (always: the ranks are the scan of the flags the total counted)
     write_entry(a.new_ids, a.new_ends, rank, load_id(a.st.ids, e), off, size, a.st.arena + old,
                 &a.segs[rank]);
+    if (a.new_stamps) a.new_stamps[rank] = a.stamps[e];
+  }
+  // a victim's place among the victims: its entry number less the survivors in front of it
+  if (a.ev_ids && e < a.st.n && !keep && e - rank < a.n_ev) {
+    const Id32 me = load_id(a.st.ids, e);
+    uint4* dst = reinterpret_cast<uint4*>(a.ev_ids + 32 * (e - rank));
+    dst[0] = me.lo;
+    dst[1] = me.hi;
+  }
   const u64 bm = __ballot(moved);
   const u64 mb = wave_sum(moved ? size : 0);
   if ((threadIdx.x & 63) == 0) {
@@ -334,6 +362,190 @@ __global__ __launch_bounds__(kStoreThreads) void store_reclaim_kernel(const uint
   if (e < st_n) idset_claim_empty(st_slots, st_mask, st_salt, load_id(st_ids, e), (uint32_t)e);
 }
 
+// ---- use tracking and eviction -------------------------------------------------------
+// One lane per ID: the entry that holds it takes the stamp.  Lanes that name
+// one entry write one value to one word.  missing (may be null) counts the
+// positions the store does not hold.  store_find answers below st.n only.
+__global__ __launch_bounds__(kStoreThreads) void store_touch_kernel(const uint8_t* ids, u64 n,
+                                                                    StoreView st, uint64_t* stamps,
+                                                                    u64 stamp, u64* missing) {
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool miss = false;
+  if (i < n) {
+    const uint32_t e = store_find(st, load_id(ids, i));
+    miss = e == kEmpty;
+    if (!miss) stamps[e] = stamp;
+  }
+  if (missing) {
+    const u64 bm = __ballot(miss);
+    if ((threadIdx.x & 63) == 0 && bm) atomicAdd(missing, (u64)__popcll(bm));
+  }
+}
+
+// One lane per ID of a copy: the source entry of a copied ID takes the stamp.
+__global__ __launch_bounds__(kStoreThreads) void store_touch_source_kernel(const uint8_t* flag,
+                                                                           const uint32_t* srce, u64 n,
+                                                                           uint64_t* stamps, u64 src_n,
+                                                                           u64 stamp) {
+  const u64 i = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  if (i < n && flag[i] && srce[i] < src_n) stamps[srce[i]] = stamp;
+}
+
+struct EvictArgs {
+  const uint8_t* pin_ids;     // the pin list ...
+  const uint32_t* pin_slots;  // ... and the table over it
+  u64 n_pin, pin_mask, pin_salt;
+  StoreView st;
+  const uint64_t* stamps;  // [st.n]
+  uint8_t* pinned;         // [st.n]
+  u64* sel;                // [kEvictSel]
+  u64* hist;               // this pass's 256 {entries, bytes} pairs
+  u64* cblk;               // the boundary class's {entries, bytes} per workgroup
+  uint8_t* flag;           // keep[e], and what store_mark_kernel leaves beside it:
+  u64* blk;
+  u64* tot;
+  u64 need_chunks, need_bytes;  // the call's, less the room the store has
+  int level, first;        // the stamp byte of this pass; first: the needs are the call's, not sel's
+};
+
+__device__ __forceinline__ u64 entry_size(const StoreView& st, u64 e) {
+  return st.ends[e] - (e ? st.ends[e - 1] : 0);
+}
+
+// One lane per entry: pinned[e] = the entry's ID is in the pin list; the sums of
+// the others.
+__global__ __launch_bounds__(kStoreThreads) void evict_pin_kernel(EvictArgs a) {
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool pin = false, free_ = false;
+  u64 size = 0;
+  if (e < a.st.n) {
+    pin = idset_find(a.pin_ids, a.n_pin, a.pin_slots, a.pin_mask, a.pin_salt, load_id(a.st.ids, e)) != kEmpty;
+    free_ = !pin;
+    if (free_) size = entry_size(a.st, e);
+    a.pinned[e] = pin ? 1 : 0;
+  }
+  const u64 bp = __ballot(pin), bf = __ballot(free_);
+  const u64 bytes = wave_sum(size);
+  if ((threadIdx.x & 63) == 0) {
+    if (bf) atomicAdd(&a.sel[kSelEvictable], (u64)__popcll(bf));
+    if (bytes) atomicAdd(&a.sel[kSelEvictableBytes], bytes);
+    if (bp) atomicAdd(&a.sel[kSelPinned], (u64)__popcll(bp));
+  }
+}
+
+// One pass of the descent, one lane per entry: an unpinned entry whose stamp
+// bytes above `level` are the ones chosen so far adds {1, size} to the bucket
+// of its byte `level`, in LDS; then one global add per non-empty sum.  A wave
+// whose entries all fall into one bucket (every pass above the byte in which
+// the stamps differ, and every pass of a store with one stamp) adds its two
+// sums once, from lane 0; a wave with several buckets adds per lane.  Integer
+// adds: the histogram does not depend on their order, nor on which way a wave went.
+__global__ __launch_bounds__(kStoreThreads) void evict_hist_kernel(EvictArgs a) {
+  __shared__ u64 s_hist[2 * dsx_evict::kBuckets];
+  if (a.sel[kSelFailed]) return;  // (the whole grid: nothing below reads the histogram)
+  for (int k = threadIdx.x; k < 2 * dsx_evict::kBuckets; k += kStoreThreads) s_hist[k] = 0;
+  __syncthreads();
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  bool mine = false;
+  uint32_t b = 0;
+  u64 size = 0;
+  if (e < a.st.n && !a.pinned[e]) {
+    const u64 s = a.stamps[e];
+    const u64 above = a.level >= 7 ? 0 : s >> (8 * (a.level + 1));
+    if (above == a.sel[kSelPrefix]) {
+      mine = true;
+      b = (uint32_t)(s >> (8 * a.level)) & 255u;
+      size = entry_size(a.st, e);
+    }
+  }
+  const u64 bm = __ballot(mine);
+  if (bm) {  // (wave-uniform)
+    const uint32_t first = __shfl(b, __ffsll((unsigned long long)bm) - 1, 64);
+    if (__ballot(mine && b == first) == bm) {
+      const u64 bytes = wave_sum(size);  // (size is 0 in the lanes without an entry)
+      if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&s_hist[2 * first], (u64)__popcll(bm));
+        if (bytes) atomicAdd(&s_hist[2 * first + 1], bytes);
+      }
+    } else if (mine) {
+      atomicAdd(&s_hist[2 * b], 1ull);
+      if (size) atomicAdd(&s_hist[2 * b + 1], size);
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < 2 * dsx_evict::kBuckets; k += kStoreThreads)
+    if (s_hist[k]) atomicAdd(&a.hist[k], s_hist[k]);
+}
+
+// One workgroup: the bucket the prefix ends in (dsx_evict_geom.h), the chosen
+// byte appended to the prefix and the needs lowered by the sums below it.
+__global__ __launch_bounds__(kStoreThreads) void evict_choose_kernel(EvictArgs a) {
+  __shared__ dsx_evict::Pair s_pair[dsx_evict::kBuckets];
+  for (int k = threadIdx.x; k < dsx_evict::kBuckets; k += kStoreThreads) {
+    s_pair[k].count = a.hist[2 * k];
+    s_pair[k].bytes = a.hist[2 * k + 1];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0 || a.sel[kSelFailed]) return;
+  const u64 nc = a.first ? a.need_chunks : a.sel[kSelNeedChunks];
+  const u64 nb = a.first ? a.need_bytes : a.sel[kSelNeedBytes];
+  const dsx_evict::Choice c = dsx_evict::choose(s_pair, nc, nb);
+  if (c.bucket < 0) {
+    a.sel[kSelFailed] = 1;
+    return;
+  }
+  a.sel[kSelPrefix] = (a.sel[kSelPrefix] << 8) | (u64)c.bucket;
+  a.sel[kSelNeedChunks] = c.need_chunks;
+  a.sel[kSelNeedBytes] = c.need_bytes;
+}
+
+// unpinned and stamped with the cutoff T: the class the prefix ends in
+__device__ __forceinline__ bool in_class(const EvictArgs& a, u64 e) {
+  return e < a.st.n && !a.sel[kSelFailed] && !a.pinned[e] && a.stamps[e] == a.sel[kSelPrefix];
+}
+
+// One lane per entry: {entries, bytes} of the boundary class per workgroup.
+__global__ __launch_bounds__(kStoreThreads) void evict_class_kernel(EvictArgs a) {
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  const bool mine = in_class(a, e);
+  const u64 bc = __ballot(mine);
+  const u64 bytes = wave_sum(mine ? entry_size(a.st, e) : 0);
+  block_totals_to<kStoreThreads, 2>({(u64)__popcll(bc), bytes}, a.cblk);
+}
+
+// One lane per entry, after the scan of cblk: keep[e] = pinned, or stamped above
+// T, or of the class T behind a class prefix that already meets the needs.
+// Leaves what store_mark_kernel leaves.
+__global__ __launch_bounds__(kStoreThreads) void evict_keep_kernel(EvictArgs a) {
+  const u64 e = (u64)blockIdx.x * kStoreThreads + threadIdx.x;
+  const bool mine = in_class(a, e);
+  const u64 my_size = e < a.st.n ? entry_size(a.st, e) : 0;
+  u64 before[2], all[2];
+  block_scan<kStoreThreads, 2>({mine ? 1ull : 0ull, mine ? my_size : 0ull}, before, all);
+  bool keep = false;
+  u64 size = 0, gone_at = 0;
+  if (e < a.st.n) {
+    if (mine) {
+      keep = a.cblk[2 * (u64)blockIdx.x] + before[0] >= a.sel[kSelNeedChunks] &&
+             a.cblk[2 * (u64)blockIdx.x + 1] + before[1] >= a.sel[kSelNeedBytes];
+    } else {
+      keep = a.sel[kSelFailed] || a.pinned[e] || a.stamps[e] > a.sel[kSelPrefix];
+    }
+    if (keep) size = my_size;
+    else if (my_size) gone_at = UINT64_MAX - (e ? a.st.ends[e - 1] : 0);
+    a.flag[e] = keep ? 1 : 0;
+  }
+  const u64 bk = __ballot(keep);
+  const u64 bytes = wave_sum(size);
+  gone_at = wave_max(gone_at);
+  if ((threadIdx.x & 63) == 0) {
+    if (bk) atomicAdd(&a.tot[0], (u64)__popcll(bk));
+    if (bytes) atomicAdd(&a.tot[1], bytes);
+    if (gone_at) atomicMax(&a.tot[2], gone_at);
+  }
+  block_totals_to<kStoreThreads, 2>({(u64)__popcll(bk), bytes}, a.blk);
+}
+
 }  // namespace dsx
 
 using namespace dsx;
@@ -349,6 +561,7 @@ void free_store(dsx_store* s) {
   s->ends.release();
   s->slots.release();
   s->arena.release();
+  s->stamps.release();
   delete s;
 }
 
@@ -380,6 +593,117 @@ int select_scan_wait(dsx_ctx* c, uint64_t items, Select&& select, u64 (&tot)[kSt
   if (distinct)
     HIPCHK(c, hipMemcpyAsync(distinct, c->idset.tot.p, sizeof *distinct, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
+  return DSX_OK;
+}
+
+// The back half of a prune and of an evict, behind the wait that read the kept
+// count and bytes and UINT64_MAX - the first removed offset into tot[]
+// (a.flag, a.blk and a.st are set, something is removed): the compaction of
+// the metadata into scratch, the windowed move of the arena, the write-back of
+// IDs, ends and a tracked store's stamps, the table rebuild, the last wait.
+// tot[4], tot[5] end as the moved entries and bytes.  A failure past the first
+// write leaves the store broken.  evicted (host, may be null): the IDs of the
+// entries that go, the first a.n_ev in entry order, read in the same wait.
+// dry: the scratch is filled and read, the store is not touched.
+int compact_tail(dsx_ctx* c, dsx_store* s, PruneArgs& a, uint64_t kept, uint64_t kept_bytes,
+                 u64 (&tot)[kStoreCounters], uint64_t window, bool dry, uint8_t* evicted) {
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint64_t T = DSX_ASSEMBLE_TILE;
+  const uint32_t blocks = blocks_of(s->chunks);
+  // ---- compact the metadata (into scratch) ---------------------------------------
+  uint64_t win = std::min<uint64_t>(window ? window : kPruneWindow, 1ull << 62);
+  win = (win + T - 1) / T * T;
+  win = std::min<uint64_t>(win, (s->arena_bytes + 15 + T) / T * T);  // (an arena's tiles: it never needs more)
+  const uint64_t first_off = tot[2] ? UINT64_MAX - tot[2] : kept_bytes;  // in front of it nothing moves
+  const bool moves = first_off < kept_bytes;
+  if (!evicted) a.n_ev = 0;
+  if (kept || a.n_ev) {
+    // (no headroom: these are sized by the store and the window, not by a call that may grow)
+    HIPCHK(c, grow(c, w.pids, kept * 32, false));
+    HIPCHK(c, grow(c, w.pends, kept, false));
+    HIPCHK(c, grow(c, w.segs, 3 * kept));
+    if (moves && !dry) HIPCHK(c, grow(c, w.bounce, win, false));
+    a.new_ids = w.pids.p;
+    a.new_ends = (uint64_t*)w.pends.p;
+    a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
+    a.n_keep = kept;
+    if (s->tracked) {
+      HIPCHK(c, grow(c, w.pstamps, kept, false));
+      a.stamps = s->stamps.p;
+      a.new_stamps = (uint64_t*)w.pstamps.p;
+    }
+    if (a.n_ev) {
+      HIPCHK(c, grow(c, w.ev_ids, a.n_ev * 32));
+      a.ev_ids = w.ev_ids.p;
+    }
+    hipLaunchKernelGGL(store_compact_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (dry) {
+    if (a.n_ev) HIPCHK(c, hipMemcpyAsync(evicted, w.ev_ids.p, a.n_ev * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return DSX_OK;
+  }
+  // ---- move, rebuild: from the first write-back on the store is in between -------
+  auto rest = [&]() -> int {
+    if (kept && moves) {
+      // Windows are whole tiles of the gather's grid over the arena's addresses;
+      // a window's gather writes bounce[0, ..) through a pointer shifted so that
+      // arena offset D = ka T - skew lands on bounce.p (16-byte aligned, as D's
+      // address is: the bounce has the arena's grid).
+      const uint64_t skew = (uintptr_t)s->arena.p & 15;
+      const uint64_t k0 = (first_off + skew) / T, k1 = (kept_bytes + skew + T - 1) / T;
+      for (uint64_t ka = k0; ka < k1; ka += win / T) {
+        const uint64_t kb = std::min<uint64_t>(ka + win / T, k1);
+        const uint64_t lo = std::max<uint64_t>(first_off, ka * T > skew ? ka * T - skew : 0);
+        const uint64_t hi = std::min<uint64_t>(kb * T - skew, kept_bytes);
+        uint8_t* out = (uint8_t*)((uintptr_t)w.bounce.p + skew - ka * T);
+        const int r = assemble_launch(c, a.segs, kept, out, hi, lo, hi, false);
+        if (r) return r;
+        HIPCHK(c, hipMemcpyAsync(s->arena.p + lo, out + lo, hi - lo, hipMemcpyDeviceToDevice, st));
+      }
+    }
+    if (kept) {
+      HIPCHK(c, hipMemcpyAsync(s->ids.p, w.pids.p, kept * 32, hipMemcpyDeviceToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(s->ends.p, w.pends.p, kept * 8, hipMemcpyDeviceToDevice, st));
+      if (s->tracked)
+        HIPCHK(c, hipMemcpyAsync(s->stamps.p, w.pstamps.p, kept * 8, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(c, hipMemsetAsync(s->slots.p, 0xFF, s->cap * sizeof(uint32_t), st));
+    if (kept) {
+      hipLaunchKernelGGL(store_reclaim_kernel, dim3(blocks_of(kept)), dim3(kStoreThreads), 0, st,
+                         (const uint8_t*)s->ids.p, (u64)kept, s->slots.p, (u64)(s->cap - 1),
+                         (u64)s->salt);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (a.n_ev) HIPCHK(c, hipMemcpyAsync(evicted, w.ev_ids.p, a.n_ev * 32, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return DSX_OK;
+  };
+  const int rc = rest();
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    s->broken = true;
+    return rc;
+  }
+  s->chunks = kept;
+  s->bytes = kept_bytes;
+  return DSX_OK;
+}
+
+// An accepted put or copy into a tracked store: every entry the call's IDs name
+// takes one new clock value.  The launch is behind the append on the stream,
+// so the table holds the appended entries (s->chunks counts them already).
+// wait: the call has nothing else left to wait for.
+int touch_accepted(dsx_ctx* c, dsx_store* s, const uint8_t* d_ids, uint64_t n, bool wait) {
+  hipLaunchKernelGGL(store_touch_kernel, dim3(blocks_of(n)), dim3(kStoreThreads), 0, c->stream, d_ids,
+                     (u64)n, view_of(s), s->stamps.p, (u64)next_stamp(s), (u64*)nullptr);
+  HIPCHK(c, hipGetLastError());
+  s->clock = next_stamp(s);
+  if (wait) HIPCHK(c, hipStreamSynchronize(c->stream));
   return DSX_OK;
 }
 
@@ -529,7 +853,7 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
              std::to_string(stored_bytes) + " bytes do not fit";
     return DSX_E_CAPACITY;
   }
-  if (!stored) return DSX_OK;
+  if (!stored) return s->tracked ? touch_accepted(c, s, a.ids, n, true) : DSX_OK;
   // ---- append, copy ------------------------------------------------------------
   HIPCHK(c, grow(c, w.segs, 3 * stored));
   a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
@@ -541,6 +865,10 @@ extern "C" int dsx_store_put(dsx_ctx_t* c, dsx_store_t* s, const void* d_blob, u
   if (rc) return rc;
   s->chunks += stored;  // (the launches are enqueued: the store has the chunks from here on)
   s->bytes += stored_bytes;
+  if (s->tracked) {
+    rc = touch_accepted(c, s, a.ids, n, false);
+    if (rc) return rc;
+  }
   HIPCHK(c, hipStreamSynchronize(st));
   return DSX_OK;
 }
@@ -753,13 +1081,12 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
   IdsetScratch& t = c->idset;
   StoreScratch& w = c->store;
   hipStream_t st = c->stream;
-  const uint64_t entries = s->chunks, T = DSX_ASSEMBLE_TILE;
+  const uint64_t entries = s->chunks;
 
   // ---- mark, scan --------------------------------------------------------------
   PruneArgs a{};
   int rc = n ? stage_ids(c, ids, n, (flags & f_ids) != 0, &a.ids) : DSX_OK;
   if (rc) return rc;
-  const uint32_t blocks = blocks_of(entries);
   const uint64_t cap = idset_table_cap(n);
   HIPCHK(c, grow(c, t.slots, cap));
   HIPCHK(c, grow(c, t.tot, kIdsetCounters));
@@ -794,67 +1121,8 @@ extern "C" int dsx_store_prune(dsx_ctx_t* c, dsx_store_t* s, const void* ids, ui
   }
   if (!removed) return DSX_OK;
 
-  // ---- compact the metadata (into scratch) ---------------------------------------
-  uint64_t win = std::min<uint64_t>(window ? window : kPruneWindow, 1ull << 62);
-  win = (win + T - 1) / T * T;
-  win = std::min<uint64_t>(win, (s->arena_bytes + 15 + T) / T * T);  // (an arena's tiles: it never needs more)
-  const uint64_t first_off = tot[2] ? UINT64_MAX - tot[2] : kept_bytes;  // in front of it nothing moves
-  const bool moves = first_off < kept_bytes;
-  if (kept) {
-    // (no headroom: these are sized by the store and the window, not by a call that may grow)
-    HIPCHK(c, grow(c, w.pids, kept * 32, false));
-    HIPCHK(c, grow(c, w.pends, kept, false));
-    HIPCHK(c, grow(c, w.segs, 3 * kept));
-    if (moves) HIPCHK(c, grow(c, w.bounce, win, false));
-    a.new_ids = w.pids.p;
-    a.new_ends = (uint64_t*)w.pends.p;
-    a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
-    a.n_keep = kept;
-    hipLaunchKernelGGL(store_compact_kernel, dim3(blocks), dim3(kStoreThreads), 0, st, a);
-    HIPCHK(c, hipGetLastError());
-  }
-  // ---- move, rebuild: from the first write-back on the store is in between -------
-  auto rest = [&]() -> int {
-    if (kept && moves) {
-      // Windows are whole tiles of the gather's grid over the arena's addresses;
-      // a window's gather writes bounce[0, ..) through a pointer shifted so that
-      // arena offset D = ka T - skew lands on bounce.p (16-byte aligned, as D's
-      // address is: the bounce has the arena's grid).
-      const uint64_t skew = (uintptr_t)s->arena.p & 15;
-      const uint64_t k0 = (first_off + skew) / T, k1 = (kept_bytes + skew + T - 1) / T;
-      for (uint64_t ka = k0; ka < k1; ka += win / T) {
-        const uint64_t kb = std::min<uint64_t>(ka + win / T, k1);
-        const uint64_t lo = std::max<uint64_t>(first_off, ka * T > skew ? ka * T - skew : 0);
-        const uint64_t hi = std::min<uint64_t>(kb * T - skew, kept_bytes);
-        uint8_t* out = (uint8_t*)((uintptr_t)w.bounce.p + skew - ka * T);
-        const int r = assemble_launch(c, a.segs, kept, out, hi, lo, hi, false);
-        if (r) return r;
-        HIPCHK(c, hipMemcpyAsync(s->arena.p + lo, out + lo, hi - lo, hipMemcpyDeviceToDevice, st));
-      }
-    }
-    if (kept) {
-      HIPCHK(c, hipMemcpyAsync(s->ids.p, w.pids.p, kept * 32, hipMemcpyDeviceToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(s->ends.p, w.pends.p, kept * 8, hipMemcpyDeviceToDevice, st));
-    }
-    HIPCHK(c, hipMemsetAsync(s->slots.p, 0xFF, s->cap * sizeof(uint32_t), st));
-    if (kept) {
-      hipLaunchKernelGGL(store_reclaim_kernel, dim3(blocks_of(kept)), dim3(kStoreThreads), 0, st,
-                         (const uint8_t*)s->ids.p, (u64)kept, s->slots.p, (u64)(s->cap - 1),
-                         (u64)s->salt);
-      HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipMemcpyAsync(tot, w.tot.p, sizeof tot, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return DSX_OK;
-  };
-  rc = rest();
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    s->broken = true;
-    return rc;
-  }
-  s->chunks = kept;
-  s->bytes = kept_bytes;
+  rc = compact_tail(c, s, a, kept, kept_bytes, tot, window, false, nullptr);
+  if (rc) return rc;
   if (totals) {
     totals->moved = tot[4];
     totals->moved_bytes = tot[5];
@@ -933,7 +1201,7 @@ extern "C" int dsx_store_copy(dsx_ctx_t* c, dsx_store_t* dst, const dsx_store_t*
              std::to_string(copied_bytes) + " bytes do not fit";
     return DSX_E_CAPACITY;
   }
-  if (!copied) return DSX_OK;
+  if (!copied) return dst->tracked ? touch_accepted(c, dst, a.ids, n, true) : DSX_OK;
   // ---- append, copy ------------------------------------------------------------
   HIPCHK(c, grow(c, w.segs, 3 * copied));
   a.segs = reinterpret_cast<AsmSeg*>(w.segs.p);
@@ -943,8 +1211,228 @@ extern "C" int dsx_store_copy(dsx_ctx_t* c, dsx_store_t* dst, const dsx_store_t*
   rc = assemble_launch(c, a.segs, copied, dst->arena.p, dst->bytes + copied_bytes, dst->bytes,
                        dst->bytes + copied_bytes, false);
   if (rc) return rc;
+  const bool carry = all && dst->chunks == 0 && dst->tracked && src->tracked;
   dst->chunks += copied;  // (the launches are enqueued: dst has the chunks from here on)
   dst->bytes += copied_bytes;
+  if (carry) {
+    // every entry of src into an empty store: entry e of dst is entry e of src, and keeps its stamp
+    HIPCHK(c, hipMemcpyAsync(dst->stamps.p, src->stamps.p, copied * 8, hipMemcpyDeviceToDevice, st));
+    dst->clock = src->clock;
+  } else {
+    if (dst->tracked) {
+      rc = touch_accepted(c, dst, a.ids, n, false);
+      if (rc) return rc;
+    }
+    if (src->tracked) {  // (the stamps are not what `const` promises of src: its entries and its arena)
+      dsx_store* from = const_cast<dsx_store*>(src);
+      hipLaunchKernelGGL(store_touch_source_kernel, dim3(blocks), dim3(kStoreThreads), 0, st,
+                         (const uint8_t*)w.flag.p, (const uint32_t*)w.srce.p, (u64)n, from->stamps.p,
+                         (u64)from->chunks, (u64)next_stamp(from));
+      HIPCHK(c, hipGetLastError());
+      from->clock = next_stamp(from);
+    }
+  }
   HIPCHK(c, hipStreamSynchronize(st));
+  return DSX_OK;
+}
+
+// ---- use tracking and eviction (include/dsx.h has the contracts) ----------------------
+namespace {
+
+int untracked_store(dsx_ctx* c) {
+  c->err = "the store does not track use: dsx_store_track comes first";
+  return DSX_E_STATE;
+}
+
+}  // namespace
+
+extern "C" int dsx_store_track(dsx_ctx_t* c, dsx_store_t* s) {
+  if (!c || !s) return DSX_E_INVAL;
+  DSX_FLUSH_BEHIND(c);
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (s->tracked) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  if (s->stamps.ensure(c->mem, s->max_chunks) != 0) return DSX_E_NOMEM;
+  HIPCHK(c, hipMemsetAsync(s->stamps.p, 0, s->stamps.n * sizeof(uint64_t), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  s->tracked = true;
+  s->clock = 0;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_touch(dsx_ctx_t* c, dsx_store_t* s, const void* ids, uint64_t n,
+                               uint64_t stamp, uint64_t* n_missing, uint32_t flags) {
+  if (!c || !s) return DSX_E_INVAL;
+  DSX_FLUSH_BEHIND(c);
+  if (n_missing) *n_missing = 0;
+  if ((flags & ~DSX_IDS_DEVICE) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (!s->tracked) return untracked_store(c);
+  if (n > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n && !ids) return invalid(c, "the IDs are missing");
+  if (n == 0) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint8_t* d_ids = nullptr;
+  const int rc = stage_ids(c, ids, n, (flags & DSX_IDS_DEVICE) != 0, &d_ids);
+  if (rc) return rc;
+  HIPCHK(c, grow(c, w.tot, kStoreCounters));
+  HIPCHK(c, hipMemsetAsync(w.tot.p, 0, kStoreCounters * sizeof(u64), st));
+  const uint64_t t = stamp == DSX_STAMP_NOW ? next_stamp(s) : stamp;
+  hipLaunchKernelGGL(store_touch_kernel, dim3(blocks_of(n)), dim3(kStoreThreads), 0, st, d_ids, (u64)n,
+                     view_of(s), s->stamps.p, (u64)t, w.tot.p);
+  HIPCHK(c, hipGetLastError());
+  u64 miss = 0;
+  HIPCHK(c, hipMemcpyAsync(&miss, w.tot.p, sizeof miss, hipMemcpyDeviceToHost, st));
+  s->clock = std::max<uint64_t>(s->clock, t);  // (the launch is enqueued: the stamps are the store's from here on)
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (n_missing) *n_missing = miss;
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_stamps(dsx_ctx_t* c, const dsx_store_t* s, uint64_t first, uint64_t n,
+                                uint64_t* stamps, uint64_t* clock, uint32_t flags) {
+  if (!c || !s) return DSX_E_INVAL;
+  DSX_FLUSH_BEHIND(c);
+  if ((flags & ~DSX_OUT_DEVICE) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (!s->tracked) return untracked_store(c);
+  if (first > s->chunks || n > s->chunks - first)
+    return invalid(c, "first + n is beyond the store's entries");
+  if (clock) *clock = s->clock;
+  if (n == 0 || !stamps) return DSX_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  HIPCHK(c, hipMemcpyAsync(stamps, s->stamps.p + first, n * 8, hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return DSX_OK;
+}
+
+extern "C" int dsx_store_evict(dsx_ctx_t* c, dsx_store_t* s, uint64_t need_bytes, uint64_t need_chunks,
+                               const void* pin_ids, uint64_t n_pin, uint8_t* evicted_ids, uint64_t cap,
+                               uint64_t window, dsx_store_evict_totals_t* totals, uint32_t flags) {
+  const uint32_t f_ids = DSX_IDS_DEVICE, f_dry = DSX_EVICT_DRY;
+  if (!c || !s) return DSX_E_INVAL;
+  DSX_FLUSH_BEHIND(c);
+  if (totals) *totals = dsx_store_evict_totals_t{};
+  if ((flags & ~(f_ids | f_dry)) != 0) return invalid(c, "unknown flag bit");
+  if (!owns(c, s)) return foreign_store(c, DSX_E_INVAL);
+  if (s->broken) return broken_store(c);
+  if (!s->tracked) return untracked_store(c);
+  if (n_pin > kCallMaxN) return invalid(c, "more IDs than a call takes (0xFFFFFFF0)");
+  if (n_pin && !pin_ids) return invalid(c, "the pinned IDs are missing");
+  HIPCHK(c, hipSetDevice(c->device));
+  c->err.clear();
+  IdsetScratch& t = c->idset;
+  StoreScratch& w = c->store;
+  hipStream_t st = c->stream;
+  const uint64_t entries = s->chunks;
+  const uint64_t room_bytes = s->arena_bytes - s->bytes, room_chunks = s->max_chunks - s->chunks;
+  // what the victims have to free: the needs less the room that is there
+  const uint64_t nb = need_bytes > room_bytes ? need_bytes - room_bytes : 0;
+  const uint64_t nc = need_chunks > room_chunks ? need_chunks - room_chunks : 0;
+  const bool select = nb || nc;  // (else the empty prefix: the pin launch alone, for the totals)
+  const int passes = dsx_evict::passes_of(s->clock);
+
+  // ---- pins, descent, boundary class, keep mask, scan ----------------------------
+  EvictArgs ea{};
+  int rc = n_pin ? stage_ids(c, pin_ids, n_pin, (flags & f_ids) != 0, &ea.pin_ids) : DSX_OK;
+  if (rc) return rc;
+  const uint32_t blocks = blocks_of(entries);
+  const uint64_t pcap = idset_table_cap(n_pin);
+  HIPCHK(c, grow(c, t.slots, pcap));
+  HIPCHK(c, grow(c, t.tot, kIdsetCounters));
+  ea.pin_salt = idset_next_salt();
+  rc = idset_enqueue_build(c, ea.pin_ids, n_pin, t.slots.p, pcap, ea.pin_salt, t.tot.p);
+  if (rc) return rc;
+  ea.pin_slots = t.slots.p;
+  ea.n_pin = n_pin;
+  ea.pin_mask = pcap - 1;
+  ea.st = view_of(s);
+  ea.stamps = s->stamps.p;
+  ea.need_chunks = nc;
+  ea.need_bytes = nb;
+  HIPCHK(c, grow(c, w.ev_pinned, entries));
+  HIPCHK(c, grow(c, w.ev_sel, kEvictSel));
+  HIPCHK(c, grow(c, w.ev_hist, 8 * 2 * (uint64_t)dsx_evict::kBuckets, false));
+  HIPCHK(c, grow(c, w.ev_blk, 2 * (uint64_t)blocks));
+  ea.pinned = w.ev_pinned.p;
+  ea.sel = w.ev_sel.p;
+  ea.cblk = w.ev_blk.p;
+  u64 tot[kStoreCounters] = {}, sel[kEvictSel] = {};
+  // ---- the one wait before anything moves ---------------------------------------
+  rc = select_scan_wait(c, entries, [&](uint32_t grid) -> int {
+    ea.flag = w.flag.p, ea.blk = w.blk.p, ea.tot = w.tot.p;
+    const dim3 g(grid), b(kStoreThreads);
+    HIPCHK(c, hipMemsetAsync(ea.sel, 0, kEvictSel * sizeof(u64), st));
+    hipLaunchKernelGGL(evict_pin_kernel, g, b, 0, st, ea);
+    HIPCHK(c, hipGetLastError());
+    if (select) {
+      HIPCHK(c, hipMemsetAsync(w.ev_hist.p, 0, (size_t)passes * 2 * dsx_evict::kBuckets * sizeof(u64), st));
+      for (int p = 0; p < passes; ++p) {
+        ea.level = passes - 1 - p;
+        ea.first = p == 0;
+        ea.hist = w.ev_hist.p + (size_t)p * 2 * dsx_evict::kBuckets;
+        hipLaunchKernelGGL(evict_hist_kernel, g, b, 0, st, ea);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(evict_choose_kernel, dim3(1), b, 0, st, ea);
+        HIPCHK(c, hipGetLastError());
+      }
+      hipLaunchKernelGGL(evict_class_kernel, g, b, 0, st, ea);
+      HIPCHK(c, hipGetLastError());
+      hipLaunchKernelGGL(block_array_scan_kernel<2>, dim3(1), dim3(kArrayScanThreads), 0, st, ea.cblk,
+                         (u64)grid, (u64*)nullptr);
+      HIPCHK(c, hipGetLastError());
+      hipLaunchKernelGGL(evict_keep_kernel, g, b, 0, st, ea);
+      HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(sel, ea.sel, sizeof sel, hipMemcpyDeviceToHost, st));
+    return DSX_OK;
+  }, tot);
+  if (rc) return rc;
+  if (totals) {
+    totals->entries = entries;
+    totals->kept = entries;
+    totals->kept_bytes = s->bytes;
+    totals->pinned = sel[kSelPinned];
+    totals->evictable = sel[kSelEvictable];
+    totals->evictable_bytes = sel[kSelEvictableBytes];
+  }
+  if (!select) return DSX_OK;
+  if (sel[kSelEvictable] < nc || sel[kSelEvictableBytes] < nb) {
+    c->err = "the store cannot make the room: " + std::to_string(sel[kSelEvictable]) + " unpinned chunks of " +
+             std::to_string(sel[kSelEvictableBytes]) + " bytes, " + std::to_string(nc) + " chunks and " +
+             std::to_string(nb) + " bytes are missing";
+    return DSX_E_CAPACITY;
+  }
+  const uint64_t kept = tot[0], kept_bytes = tot[1];
+  if (sel[kSelFailed] || kept >= entries || kept_bytes > s->bytes) {
+    c->err = "the eviction's selection is inconsistent with the store's entries";
+    return DSX_E_INTERNAL;
+  }
+  const uint64_t evicted = entries - kept;
+  if (totals) {
+    totals->kept = kept;
+    totals->kept_bytes = kept_bytes;
+    totals->evicted = evicted;
+    totals->evicted_bytes = s->bytes - kept_bytes;
+    totals->cutoff = sel[kSelPrefix];
+  }
+  PruneArgs a{};
+  a.st = ea.st;
+  a.flag = w.flag.p, a.blk = w.blk.p, a.tot = w.tot.p;
+  a.n_ev = evicted_ids ? std::min<uint64_t>(cap, evicted) : 0;
+  rc = compact_tail(c, s, a, kept, kept_bytes, tot, window, (flags & f_dry) != 0, evicted_ids);
+  if (rc) return rc;
+  if (totals) {
+    totals->moved = tot[4];
+    totals->moved_bytes = tot[5];
+  }
   return DSX_OK;
 }

@@ -446,7 +446,10 @@ def AssembleBlob(index: Index, store, seeds=(), null_seed=True, limit=0, ctx=Non
         store = store.l
     if isinstance(store, DeviceStore) and store.ctx is ctx:
         # the chunks are in HBM already: point the plan's store segments at the
-        # arena (dsx_store_resolve) and gather out of it in place
+        # arena (dsx_store_resolve) and gather out of it in place; a tracked store
+        # counts them as used first
+        if store.tracked and len(plan.store_chunks):
+            store.Touch(sq.ids[plan.store_chunks])
         miss, wrong, bad = store.resolve(sq.ids, plan.segs)
         if miss or wrong:
             cid = raw[32 * bad:32 * bad + 32]
@@ -566,6 +569,8 @@ def assemble_blob_inplace(index, store, seeds, null_seed, limit, ctx, validate, 
         Copy(sq.ids[np.unique(segs["first"][sm])], store.s, store.l)
         store = store.l
     if isinstance(store, DeviceStore) and store.ctx is ctx:
+        if store.tracked and sm.any():
+            store.Touch(sq.ids[np.unique(segs["first"][sm])])
         miss, wrong, bad = store.resolve(sq.ids, segs)
         if miss or wrong:
             cid = raw[32 * bad:32 * bad + 32]

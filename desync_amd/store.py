@@ -22,6 +22,12 @@ remove chunks and compact the arena where it lies (dsx_store_prune), giving
 the room back to later puts.  ``CopyFrom`` appends chunks of another store of the
 same context (dsx_store_copy; copy.py has ``Copy`` and ``Cache``), and ``Grow``
 moves the store into a new capacity with it.
+``DeviceStore(track=True)`` keeps one use stamp per entry (dsx_store_track);
+``Touch`` says what counts as a use, ``Evict`` removes the least recently used
+chunks until a requested room is free (dsx_store_evict: the victims are chosen
+on the GPU, then the arena is compacted as a prune compacts it), and
+``DeviceStore(evict=True)`` does that by itself when a put or a copy does not
+fit: a store of fixed size that is a bounded cache.
 ``Seal`` / ``PutSealed`` convert its chunks to and from the records of a store
 with ``encryption: true`` (XChaCha20-Poly1305 on the GPU, encrypt.py), and
 ``WriteLocal`` / ``ReadLocal`` save and reload it in LocalStore's layout, plain
@@ -125,16 +131,28 @@ class DeviceStore:
     bytes: the slow path, kept so that ChunkStorage and ChunkStream work with
     it).  ``put`` / ``put_index`` store every chunk of a blob resident in HBM
     in one call.  Every call holds the store's lock: ChunkStream's workers call
-    StoreChunk from several threads, and a context is not thread-safe."""
+    StoreChunk from several threads, and a context is not thread-safe.
 
-    def __init__(self, arena_bytes, max_chunks, ctx=None, device=0):
+    ``track``: the store keeps a use stamp per entry from the start
+    (:meth:`Track` turns it on later; it cannot be turned off).  ``evict``
+    (implies ``track``): ``put``, ``put_index``, ``StoreChunk`` and ``CopyFrom``
+    that get DSX_E_CAPACITY evict the least recently used chunks for exactly
+    the missing room, with the call's own IDs pinned, and repeat the call once;
+    if the eviction cannot make the room the capacity error is raised and the
+    store is unchanged."""
+
+    def __init__(self, arena_bytes, max_chunks, ctx=None, device=0, track=False, evict=False):
         self.ctx = ctx or _lib.default_context(device)
         self.h = None
         self._lock = threading.RLock()
+        self.tracked = False
+        self.evict = bool(evict)
         h = ctypes.c_void_p()
         _check(lib().dsx_store_create(self.ctx.h, int(arena_bytes), int(max_chunks), ctypes.byref(h)),
                self.ctx)
         self.h = h
+        if track or evict:
+            self.Track()
 
     # ---- the fill state ------------------------------------------------------------
     def counts(self):
@@ -167,6 +185,91 @@ class DeviceStore:
                                                ends.ctypes.data, 0), self.ctx)
             return ids, ends
 
+    # ---- use tracking and eviction ------------------------------------------------------
+    def _state_check(self, rc):
+        if rc == _lib.DSX_E_STATE:
+            d = lib().dsx_last_error(self.ctx.h)
+            raise DsxError(rc, d.decode() if d else "")
+        return _check(rc, self.ctx)
+
+    def Track(self):
+        """dsx_store_track: one use stamp per entry from now on (the entries
+        already there start at 0).  Idempotent; cannot be turned off."""
+        with self._lock:
+            self._state_check(lib().dsx_store_track(self.ctx.h, self.h))
+            self.tracked = True
+
+    def Touch(self, ids, stamp=None, n=None):
+        """dsx_store_touch: counts the chunks ``ids`` (as for :class:`IDSet`: host
+        or device; an :class:`Index` too) as used now, or at the caller's own
+        logical time ``stamp`` (> 0).  IDs the store does not hold are no error
+        -> their number."""
+        from .index import Index
+        if isinstance(ids, Index):
+            ids = _host_ids(ids)
+        iptr, n, flags, _keep = _ids_arg(ids, n)
+        miss = ctypes.c_uint64()
+        with self._lock:
+            self._state_check(lib().dsx_store_touch(self.ctx.h, self.h, ctypes.c_void_p(iptr), n,
+                                                    _lib.DSX_STAMP_NOW if stamp is None else int(stamp),
+                                                    ctypes.byref(miss), flags))
+        return miss.value
+
+    def stamps(self):
+        """dsx_store_stamps -> (the entries' stamps as np.uint64, the clock)."""
+        with self._lock:
+            n = self.counts()["chunks"]
+            out = np.empty(n, dtype=np.uint64)
+            clock = ctypes.c_uint64()
+            self._state_check(lib().dsx_store_stamps(self.ctx.h, self.h, 0, n, out.ctypes.data,
+                                                     ctypes.byref(clock), 0))
+            return out, clock.value
+
+    def Evict(self, need_bytes=0, need_chunks=0, pin=None, window=0, dry=False, n_pin=None, ids=True):
+        """dsx_store_evict: removes the least recently used chunks, in ascending
+        (stamp, entry number), until ``need_bytes`` bytes and ``need_chunks``
+        chunks are free, and compacts the arena in place.  Chunks whose ID is in
+        ``pin`` (as for :class:`IDSet`: host or device) are never removed.
+        ``dry`` selects and reports without changing the store.  Returns the
+        dsx_store_evict_totals_t as a dict plus ``"ids"``, the evicted IDs as an
+        ``(evicted, 32)`` array in their old entry order.  Room that cannot be
+        made raises DsxError (DSX_E_CAPACITY) with ``.totals`` (evictable,
+        evictable_bytes, pinned) and leaves the store unchanged.  Arena offsets
+        taken before are stale afterwards, as after a prune.  ``ids=False``: the
+        victims' IDs are not read back (no ``"ids"`` in the result)."""
+        if pin is None:
+            iptr, n_pin, flags, _keep = 0, 0, 0, None
+        else:
+            iptr, n_pin, flags, _keep = _ids_arg(pin, n_pin)
+        if dry:
+            flags |= _lib.DSX_EVICT_DRY
+        tot = _lib.StoreEvictTotals()
+        with self._lock:
+            cap = self.counts()["chunks"] if ids else 0
+            out = np.empty((max(1, cap), 32), dtype=np.uint8) if ids else None
+            rc = lib().dsx_store_evict(self.ctx.h, self.h, int(need_bytes), int(need_chunks),
+                                       ctypes.c_void_p(iptr), n_pin, out.ctypes.data if ids else None, cap,
+                                       int(window), ctypes.byref(tot), flags)
+            totals = {k: getattr(tot, k) for k, _ in _lib.StoreEvictTotals._fields_ if k != "reserved"}
+            try:
+                self._state_check(rc)
+            except DsxError as e:
+                e.totals = totals
+                raise
+        if ids:
+            totals["ids"] = out[:totals["evicted"]].copy()
+        return totals
+
+    def _make_room(self, err, chunks, nbytes, pin, n_pin):
+        """A put or a copy got DSX_E_CAPACITY (``err``): evicts for exactly what it
+        lacks, its own IDs pinned.  Raises ``err`` if that room cannot be made."""
+        try:
+            self.Evict(need_bytes=nbytes, need_chunks=chunks, pin=pin, n_pin=n_pin, ids=False)
+        except DsxError as e:
+            if e.code == _lib.DSX_E_CAPACITY:
+                raise err from None
+            raise
+
     # ---- the write side --------------------------------------------------------------
     def put(self, blob, ids, ends, start=0, n=None):
         """dsx_store_put: stores the chunks [start, ends[0]), [ends[0], ends[1]),
@@ -194,15 +297,21 @@ class DeviceStore:
             eptr = _keep_ends.ctypes.data
         tot = _lib.StorePutTotals()
         with self._lock:
-            rc = lib().dsx_store_put(self.ctx.h, self.h, ctypes.c_void_p(ptr), length,
-                                     ctypes.c_void_p(iptr), ctypes.c_void_p(eptr), int(start), n,
-                                     ctypes.byref(tot), flags)
-            totals = {k: getattr(tot, k) for k, _ in _lib.StorePutTotals._fields_}
-            try:
-                _check(rc, self.ctx)
-            except DsxError as e:
-                e.totals = totals
-                raise
+            for attempt in (0, 1):
+                rc = lib().dsx_store_put(self.ctx.h, self.h, ctypes.c_void_p(ptr), length,
+                                         ctypes.c_void_p(iptr), ctypes.c_void_p(eptr), int(start), n,
+                                         ctypes.byref(tot), flags)
+                totals = {k: getattr(tot, k) for k, _ in _lib.StorePutTotals._fields_}
+                try:
+                    _check(rc, self.ctx)
+                except DsxError as e:
+                    e.totals = totals
+                    if e.code != _lib.DSX_E_CAPACITY or not self.evict or attempt:
+                        raise
+                    self._make_room(e, totals["stored"], totals["stored_bytes"],
+                                    iptr if flags & _lib.DSX_IDS_DEVICE else _keep_ids, n)
+                    continue
+                break
         return totals
 
     def put_index(self, blob, index):
@@ -264,6 +373,8 @@ class DeviceStore:
             offs, sizes, miss = self.locate([cid])
             if miss:
                 raise ChunkMissing(cid)
+            if self.tracked:
+                self.Touch([cid])
             size = int(sizes[0])
             out = np.empty(size, dtype=np.uint8)
             if size:
@@ -276,7 +387,8 @@ class DeviceStore:
         """:func:`desync_amd.read_ranges` of this store, under its lock: the byte
         ranges ``ranges`` of the blob ``index`` (an :class:`Index` or a
         :class:`DeviceIndex`) describes, in one dsx_read_ranges call
-        -> (device tensor, totals)."""
+        -> (device tensor, totals).  A read stamps nothing in a tracked store:
+        ``Touch(index)`` when a read should count as a use."""
         from .readseeker import read_ranges
         with self._lock:
             return read_ranges(index, self, ranges, out=out)
@@ -375,15 +487,36 @@ class DeviceStore:
         tot = _lib.StoreCopyTotals()
         first, second = sorted((self, src), key=id)  # (one lock order for every pair)
         with first._lock, second._lock:
-            rc = lib().dsx_store_copy(self.ctx.h, self.h, src.h, ctypes.c_void_p(iptr), n,
-                                      ctypes.byref(tot), flags)
-            totals = {k: getattr(tot, k) for k, _ in _lib.StoreCopyTotals._fields_ if k != "reserved"}
-            try:
-                _check(rc, self.ctx)
-            except DsxError as e:
-                e.totals = totals
-                raise
+            for attempt in (0, 1):
+                rc = lib().dsx_store_copy(self.ctx.h, self.h, src.h, ctypes.c_void_p(iptr), n,
+                                          ctypes.byref(tot), flags)
+                totals = {k: getattr(tot, k) for k, _ in _lib.StoreCopyTotals._fields_ if k != "reserved"}
+                try:
+                    _check(rc, self.ctx)
+                except DsxError as e:
+                    e.totals = totals
+                    if e.code != _lib.DSX_E_CAPACITY or not self.evict or attempt:
+                        raise
+                    if ids is None:  # (every entry of src: its IDs, copied inside HBM)
+                        pin, n_pin, _pin_keep = src._device_ids()
+                    else:
+                        pin, n_pin = (iptr if flags & _lib.DSX_IDS_DEVICE else _keep), n
+                    self._make_room(e, totals["copied"], totals["copied_bytes"], pin, n_pin)
+                    continue
+                break
         return totals
+
+    def _device_ids(self):
+        """-> (device pointer, count, the tensor that holds them): the entries'
+        IDs in a device tensor, copied there without crossing to the host."""
+        import torch
+        n = self.counts()["chunks"]
+        t = torch.empty((max(1, n), 32), dtype=torch.uint8, device=f"cuda:{self.ctx.device}")
+        torch.cuda.synchronize(t.device)  # (torch's stream, not the context's)
+        if n:
+            _check(lib().dsx_store_entries(self.ctx.h, self.h, 0, n, ctypes.c_void_p(t.data_ptr()), None,
+                                           _lib.DSX_OUT_DEVICE), self.ctx)
+        return t.data_ptr(), n, t
 
     def Grow(self, arena_bytes, max_chunks):
         """Gives the store a new capacity: creates a store of ``arena_bytes``
@@ -393,12 +526,18 @@ class DeviceStore:
         current fill the copy raises DsxError (DSX_E_CAPACITY) and the store
         stays as it was.  The arena's address changes: offsets taken before
         (``arena``, ``locate``, a resolved plan) are stale afterwards, as after
-        a prune.  Needs the memory of both stores while it runs.  Returns the
-        copy's totals."""
+        a prune.  Needs the memory of both stores while it runs.  A tracked store
+        stays tracked and keeps its stamps, its clock and so its use order.
+        Returns the copy's totals."""
         with self._lock:
             h = ctypes.c_void_p()
             _check(lib().dsx_store_create(self.ctx.h, int(arena_bytes), int(max_chunks), ctypes.byref(h)),
                    self.ctx)
+            if self.tracked:  # (the copy of every entry into an empty tracked store carries the stamps)
+                rc = lib().dsx_store_track(self.ctx.h, h)
+                if rc < 0:
+                    lib().dsx_store_destroy(self.ctx.h, h)
+                    _check(rc, self.ctx)
             tot = _lib.StoreCopyTotals()
             rc = lib().dsx_store_copy(self.ctx.h, h, self.h, None, 0, ctypes.byref(tot), _lib.DSX_COPY_ALL)
             totals = {k: getattr(tot, k) for k, _ in _lib.StoreCopyTotals._fields_ if k != "reserved"}

@@ -1056,6 +1056,112 @@ typedef struct dsx_store_prune_totals {
 int dsx_store_prune(dsx_ctx_t *ctx, dsx_store_t *store, const void *ids, uint64_t n,
                     uint64_t window, dsx_store_prune_totals_t *totals, uint32_t flags);
 
+/* ---- use tracking and eviction: what makes a store of fixed size a cache --------------
+ * The reference has no eviction (cache.go grows without bound and leaves the
+ * cleanup to desync prune); nothing here changes what it defines.  Everything
+ * is opt-in per store: a store that never calls dsx_store_track allocates
+ * nothing more, launches nothing more and behaves as above.
+ *
+ * dsx_store_track allocates one uint64_t stamp per possible entry (max_chunks
+ * words, counted in device_bytes, freed with the store), sets the stamp of
+ * every entry already there to 0 and starts the store's clock, a host counter,
+ * at 0.  A second call changes nothing; tracking cannot be turned off.  A store
+ * of another context: DSX_E_INVAL; a broken one: DSX_E_STATE.
+ *
+ * The use order of a tracked store is total: ascending (stamp, entry number).
+ * Among entries with equal stamps the one appended earlier is older.  From
+ * dsx_store_track on:
+ *   - dsx_store_put and dsx_store_copy into a tracked store take one new clock
+ *     value t = ++clock when accepted and stamp with t every entry the call's
+ *     IDs name, appended or found present (one more launch over the call's IDs
+ *     behind the append).  A refused call (DSX_E_CAPACITY, DSX_E_INVAL, a copy
+ *     with missing > 0) and a call with n == 0 stamp nothing and leave the clock.
+ *   - a tracked source of a copy that copied something takes its own ++clock on
+ *     the entries that were copied (the stamps and the clock are the one thing
+ *     a copy changes of src).
+ *   - DSX_COPY_ALL from a tracked source into an empty tracked destination
+ *     carries the stamps over instead: entry e of dst gets the stamp of entry e
+ *     of src, dst's clock becomes src's, and src is not stamped.  A store grown
+ *     by such a copy keeps its use order.
+ *   - dsx_store_prune carries the survivors' stamps with their IDs and ends.
+ *   - The read calls stamp nothing: dsx_store_locate, dsx_store_resolve,
+ *     dsx_read_ranges, dsx_chunk_ids_known, dsx_store_verify, dsx_store_entries
+ *     and dsx_assemble run exactly as for an untracked store.  What counts as a
+ *     use is the caller's decision, said with dsx_store_touch. */
+int dsx_store_track(dsx_ctx_t *ctx, dsx_store_t *store);
+
+/* Stamps the entries that hold ids[] (n 32-byte IDs, host memory, or device
+ * memory with DSX_IDS_DEVICE; duplicates allowed).  stamp == DSX_STAMP_NOW: the
+ * value is ++clock.  Any other stamp is written as given and clock becomes
+ * max(clock, stamp): a caller may use its own logical time, such as a training
+ * step.  The clock saturates at UINT64_MAX and never wraps: once a caller's
+ * stamp has taken it there, every later ++clock, of a put or a copy too,
+ * hands out UINT64_MAX again, and those uses are ordered by entry number alone.
+ * IDs the store does not hold are no error; *n_missing (may be NULL)
+ * counts the positions not held.  n == 0: DSX_OK, the clock does not advance.
+ * Any flag bit other than DSX_IDS_DEVICE, n > 0xFFFFFFF0, ids == NULL with
+ * n > 0, a store of another context: DSX_E_INVAL; an untracked or a broken
+ * store: DSX_E_STATE with a dsx_last_error text.  Synchronous on the ctx
+ * stream: one launch, one host wait. */
+#define DSX_STAMP_NOW 0ull
+int dsx_store_touch(dsx_ctx_t *ctx, dsx_store_t *store, const void *ids, uint64_t n,
+                    uint64_t stamp, uint64_t *n_missing, uint32_t flags);
+
+/* The stamps of entries [first, first + n) (host memory, or device memory with
+ * DSX_OUT_DEVICE; may be NULL) and the clock (may be NULL), as
+ * dsx_store_entries gives IDs and ends.  An untracked store: DSX_E_STATE. */
+int dsx_store_stamps(dsx_ctx_t *ctx, const dsx_store_t *store, uint64_t first, uint64_t n,
+                     uint64_t *stamps, uint64_t *clock, uint32_t flags);
+
+#define DSX_EVICT_DRY 8192u /* select, fill the totals and evicted_ids; change nothing of the store */
+
+typedef struct dsx_store_evict_totals {
+    uint64_t entries;                 /* before the call */
+    uint64_t evicted, evicted_bytes;
+    uint64_t kept, kept_bytes;
+    uint64_t moved, moved_bytes;      /* as dsx_store_prune counts them */
+    uint64_t pinned;                  /* entries the pin list protected */
+    uint64_t evictable, evictable_bytes; /* unpinned entries and their bytes, before the call */
+    uint64_t cutoff;                  /* the largest stamp evicted, 0 if none */
+    uint64_t reserved[2];             /* 0 */
+} dsx_store_evict_totals_t;          /* 104 bytes */
+
+/* Removes the least recently used entries of a tracked store until there is
+ * room for need_bytes bytes and need_chunks chunks, and compacts the arena as
+ * dsx_store_prune does.  The contract is exact and the same on every run:
+ * let U be the entries whose ID is not among pin_ids[] (n_pin 32-byte IDs,
+ * host memory, or device memory with DSX_IDS_DEVICE; duplicates allowed; IDs
+ * the store does not hold are ignored), in ascending (stamp, entry number).
+ * The call removes the shortest prefix P of U with
+ *     arena_bytes - bytes + bytes(P) >= need_bytes   and
+ *     max_chunks - chunks + |P| >= need_chunks.
+ * Zero-length entries count as chunks only.  If the empty prefix suffices the
+ * call changes no arena byte, entry, stamp or table slot and returns DSX_OK;
+ * if not even all of U suffices it returns DSX_E_CAPACITY, the store is
+ * unchanged and the totals hold entries, pinned, evictable and
+ * evictable_bytes (kept and kept_bytes are the store's).
+ * evicted_ids (host memory, may be NULL) receives the IDs of the evicted
+ * entries in ascending old entry number, min(cap, evicted) of them.
+ * Survivors keep their relative order, are renumbered and keep their stamps;
+ * the arena is packed at the same address.  Everything dsx_store_prune says of
+ * stale offsets, of `window`, of dsx_cancel and of the broken state after a
+ * HIP failure past the first write holds here too.
+ * DSX_EVICT_DRY: the selection, the totals (moved and moved_bytes included)
+ * and evicted_ids of the call without it; the store is not changed.
+ * The victims are chosen on the device (Eviction): the stamps
+ * and the pin list never cross to the host.
+ * Refused before any device work: an untracked store (DSX_E_STATE with a
+ * dsx_last_error text), a broken one (DSX_E_STATE), a store of another context,
+ * n_pin > 0xFFFFFFF0, pin_ids == NULL with n_pin > 0, any flag bit other than
+ * DSX_IDS_DEVICE and DSX_EVICT_DRY (DSX_E_INVAL).
+ * Synchronous on the ctx stream: one host wait after the selection (the totals
+ * and the capacity decision) and one at the end. */
+int dsx_store_evict(dsx_ctx_t *ctx, dsx_store_t *store,
+                    uint64_t need_bytes, uint64_t need_chunks,
+                    const void *pin_ids, uint64_t n_pin,
+                    uint8_t *evicted_ids, uint64_t cap, uint64_t window,
+                    dsx_store_evict_totals_t *totals, uint32_t flags);
+
 /* Copy (copy.go:9-58; desync cache, and what a Cache in front of a store does
  * with every chunk it fetches, cache.go:24-45) between two stores of one
  * context, and what growing a store is made of: DSX_COPY_ALL into a new store
